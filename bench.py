@@ -30,14 +30,14 @@ Rank 0 prints ONE JSON line with the contract fields plus
                       <= 40 classes, each step = a NEW batch of images x 31 forwards (the LVIS protocol of
                       engine/inference.py:605-625) with the boundary's caches ON; value = forwards/s, plus LVIS-style
                       images/s = forwards/s / 31.
+    --dump-outputs DIR  after the timed steps, what the LAST timed step returned to its caller -- per image the boxes, scores and
+                      labels of its BoxList -- as DIR/out<i>_<field>.npy (float32 / float64, at most 64 MB).  Inputs, weights and
+                      captions are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
 import os
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")        # mq_det_amd.RECOMMENDED_ENV: read when the HIP runtime initialises, so before `import torch`
-
-import statistics  # noqa: E402
+import statistics
 import sys
 import tempfile
 import time
@@ -72,6 +72,47 @@ def executed_gflop_per_image(n_tok, layers=6, swin=198.2):
     per_layer = vlfuse_attn + 2.4 + 3.83 + 42.4
     heads = 2.0 * N * 256 * (k16 + 16) / 1e9
     return swin + 29.3 + 45.9 + 7.5 + 17.9 + layers * per_layer + heads
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def outputs_to_host(out):
+    """What a caller of the timed path receives (list[BoxList], or a nested list of them), flattened to named float arrays on the host:
+    <prefix>_bbox [n, 4] plus one array per extra field.  Called right after the timed region, before any later forward can reuse the
+    buffers the captured graph writes."""
+    import numpy as np
+    arrays = {}
+
+    def visit(obj, prefix):
+        if isinstance(obj, (list, tuple)):
+            for i, o in enumerate(obj):
+                visit(o, f"{prefix}{i}" if prefix.endswith("out") else f"{prefix}_{i}")
+        elif isinstance(obj, dict):
+            for k, v in obj.items():
+                visit(v, f"{prefix}_{k}")
+        elif hasattr(obj, "bbox") and hasattr(obj, "extra_fields"):
+            visit(obj.bbox, f"{prefix}_bbox")
+            for k, v in obj.extra_fields.items():
+                visit(v, f"{prefix}_{k}")
+        elif isinstance(obj, torch.Tensor):
+            t = obj.detach().cpu()
+            t = t.double() if t.dtype in (torch.float64, torch.int64, torch.int32) else t.float()
+            arrays[prefix] = np.ascontiguousarray(t.numpy())
+    visit(out, "out")
+    return arrays
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64), at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": int(total)}
 
 
 def build_model(dev, caches=False, n_classes=NUM_CLASSES_IN_CAPTION, n_categories=None, large=False, words=None, dtype="f16"):
@@ -186,6 +227,7 @@ def main_gdino(args, rank, world, dev):
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    dumped = outputs_to_host(out) if args.dump_outputs and rank == 0 else None
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
@@ -233,6 +275,8 @@ def main_gdino(args, rank, world, dev):
                                        "corner rows the gather pulls through L2 -> L1 (the real bound, DESIGN.md 11)"}
         if world == 1 and args.cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(timeout=300, flag="--cpu-baseline-worker-gdino")
+        if dumped is not None:
+            res["dumped_outputs"] = dump_outputs(dumped, args.dump_outputs)
         print(compact_line(res, args.extras_file or os.path.join(ROOT, "bench_extras_gdino.json"), write=bool(args.extras_file) or not args.no_extras), flush=True)
     if world > 1:
         torch.distributed.barrier()
@@ -240,6 +284,12 @@ def main_gdino(args, rank, world, dev):
 
 
 CPU_BASELINE_THREADS = 32      # the oracle's many small torch ops stop scaling (and can crawl) far below 256 threads
+
+
+def _cpu_baseline_threads():
+    """CPU_BASELINE_THREADS, capped by the host's cores and by an OMP_NUM_THREADS the environment already sets (a shared host's CPU share)."""
+    cap = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(os.cpu_count() or 1, CPU_BASELINE_THREADS, int(cap) if cap.isdigit() and int(cap) > 0 else CPU_BASELINE_THREADS))
 
 
 def _cpu_baseline_worker():
@@ -251,7 +301,7 @@ def _cpu_baseline_worker():
     from oracle import glip_t_spec
     from oracle import detector as od
     from oracle.weights import make_state_dict, make_query_bank
-    threads = min(os.cpu_count() or 1, CPU_BASELINE_THREADS)
+    threads = _cpu_baseline_threads()
     torch.set_num_threads(threads)
     g = torch.Generator().manual_seed(0)
     images, sizes = od.pad_images([torch.randn(3, *IMG_HW, generator=g)], 32)
@@ -295,7 +345,7 @@ def _cpu_baseline_worker_gdino():
     from oracle import gdino as og
     from oracle.spec import gdino_t_spec
     from oracle.weights import make_gdino_state_dict
-    threads = min(os.cpu_count() or 1, CPU_BASELINE_THREADS)
+    threads = _cpu_baseline_threads()
     torch.set_num_threads(threads)
     spec = gdino_t_spec(vocab=30522, vision_query=False)
     sd = make_gdino_state_dict(spec, 0)
@@ -327,7 +377,8 @@ def _cpu_baseline_worker_gdino():
 def cpu_baseline_start(flag="--cpu-baseline-worker"):
     """Start the CPU-oracle worker (its own process, pinned threads, no GPU visible)."""
     import subprocess
-    env = dict(os.environ, OMP_NUM_THREADS=str(CPU_BASELINE_THREADS), MKL_NUM_THREADS=str(CPU_BASELINE_THREADS),
+    threads = str(_cpu_baseline_threads())
+    env = dict(os.environ, OMP_NUM_THREADS=threads, MKL_NUM_THREADS=threads,
                OMP_PLACES="cores", OMP_PROC_BIND="close", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     return subprocess.Popen([sys.executable, os.path.abspath(__file__), flag], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
 
@@ -626,9 +677,9 @@ def _sub_bench(argv, env=None, timeout=150, keep=()):
         return {"error": f"worker exceeded {timeout} s"}
 
 
-# every operator with two implementations on the one that was the default at the end of ROUND 3 (ops.KERNEL_DEFAULTS lists today's), and the
-# runtime default of the hardware queues: what round 4's switchable changes buy (not switchable, so inside both runs: the VLFuse softmax diet)
-ROUND3_KERNEL_SET = {"MQ_POST_FUSED": "0", "MQ_BERT_QKV_FUSED": "0", "MQ_PATCH_EMBED_FUSED": "0", "MQ_OFFSET_CONV_VARIANT": "2", "GPU_MAX_HW_QUEUES": "4"}
+# every operator with two implementations on the one that was the default at the end of ROUND 3 (ops.KERNEL_DEFAULTS lists today's):
+# what round 4's switchable changes buy (not switchable, so inside both runs: the VLFuse softmax diet)
+ROUND3_KERNEL_SET = {"MQ_POST_FUSED": "0", "MQ_BERT_QKV_FUSED": "0", "MQ_PATCH_EMBED_FUSED": "0", "MQ_OFFSET_CONV_VARIANT": "2"}
 # ... and what ROUND 5's switchable changes buy: the text on all 256 padded positions, the BERT / GCP attention halves as the launches of round 4,
 # the FPN convs through the general DCNv2 instantiation, the DyConv epilogue per level on five streams (not switchable, so inside both runs: the
 # Swin MLP tail kernel with its loads in flight)
@@ -728,6 +779,8 @@ def main():
     ap.add_argument("--cpu-baseline", action="store_true", help="mq-gdino-t workload: also time the CPU oracle (off by default there)")
     ap.add_argument("--overlap-gather", action="store_true", help="N > 1: the gather of step k runs asynchronously under the forward of step k + 1 "
                                                                   "(parallel.OverlappedGather); the last one is waited for inside the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                                                                         "(boxes, scores, labels per image) as DIR/<name>.npy")
     ap.add_argument("--dry-launch", action="store_true", help="launcher check: start the ranks, rendezvous, one fixed-shape gather of dummy "
                                                               "detections, print the line with n_gpus = ranks; no kernels (runs on CPU over gloo)")
     args = ap.parse_args()
@@ -739,6 +792,8 @@ def main():
         args.no_experimental = args.no_lang_b64 = args.no_cpu_baseline = True
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher around it: start the N ranks ourselves, one process per GPU
         # (the reference: `python -m torch.distributed.launch --nproc_per_node=N tools/test_grounding_net.py`, :35-60)
@@ -825,6 +880,7 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    dumped = outputs_to_host(out) if args.dump_outputs and rank == 0 else None
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
@@ -925,6 +981,8 @@ def main():
                     res["cpu_baseline"] = cpu_baseline()
                 except Exception as e:  # noqa: BLE001
                     res["cpu_baseline"] = {"error": repr(e)[:200]}
+        if dumped is not None:
+            res["dumped_outputs"] = dump_outputs(dumped, args.dump_outputs)
         print(compact_line(res, args.extras_file, write=bool(args.extras_file) or not args.no_extras), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -1,9 +1,9 @@
 """Drop-in evidence: the product model is built from the reference's REAL config tree
 (`maskrcnn_benchmark/config/defaults.py` + `configs/pretrain/mq-glip-t.yaml` + `configs/vision_query_5shot/lvis_minival.yaml`,
-loaded in place through oracle/_refload.py) and driven through the reference's own caller sequence:
+as recorded from the reference) and driven through the reference's own caller sequence:
 
   * captions / positive maps come from the reference's `create_queries_and_maps_from_dataset` (engine/inference.py:195-283,
-    executed in place) on an LVIS-like category list, chunked by TEST.CHUNKED_EVALUATION = 40;
+    recorded) on an LVIS-like category list, chunked by TEST.CHUNKED_EVALUATION = 40;
   * the loop body is engine/inference.py:599-643: `images.to(device)`, one `model(images, captions=, positive_map=)` per chunk,
     `[o.to(cpu_device) for o in output]`, `resize_box`, `.extra_fields["scores"|"labels"]`, `.bbox` -- the LVIS branch;
   * tools/test_grounding_net.py:141-154: `build_detection_model(cfg)`, `model.to(cfg.MODEL.DEVICE)` (skipped: no GPU here),
@@ -12,29 +12,103 @@ loaded in place through oracle/_refload.py) and driven through the reference's o
 The box has no GPU, so the HIP entry points are swapped for the test-only torch emulations (tests/ops_emulation.py) -- what is
 under test here is the BOUNDARY: every cfg attribute the product reads exists in the reference tree, the call signatures,
 return types and BoxList methods the callers use, and (against the oracle on the same weights) the results.
-Needs /root/reference (build container only)."""
+What the reference's own code returns -- its config trees, the captions / positive maps of its caption builders, resize_box, what
+GLIPDemo hands to the model and its post-processing order -- was recorded by executing that code in place (oracle/gen_golden_dropin.py)
+and is read from tests/golden/dropin_reference.json."""
+import json
 import os
 import sys
 import tempfile
-import types
 
 import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container)")
-
 LVIS_LIKE = ["aerosol_can", "air_conditioner", "airplane", "alarm_clock", "alcohol", "alligator", "almond", "ambulance", "amplifier",
              "anklet", "antenna", "apple", "applesauce", "apricot", "apron", "aquarium", "arctic_(type_of_shoe)", "armband", "armchair",
              "armoire", "armor", "artichoke", "trash_can", "ashtray", "asparagus", "atomizer", "avocado", "award", "awning", "ax",
              "baboon", "baby_buggy", "basketball_backboard", "backpack", "handbag", "suitcase", "bagel", "bagpipe", "baguet", "bait",
              "ball", "ballet_skirt", "balloon", "bamboo", "banana", "Band_Aid", "bandage", "bandanna", "banjo", "banner"]
+GLIPDEMO_NAMES = ["person", "sports ball", "traffic light", "dog"]
+GLIPDEMO_THRESHOLD = 0.06
 
 
-def test_reference_cfg_tree_and_caller_sequence(monkeypatch):
+def words_of(names):
+    """The words of LVIS-style category names (the vocabulary the synthetic tokenizer gets on top of its own)."""
+    return [w for n in names for w in n.lower().replace("(", " ").replace(")", " ").replace("_", " ").split()]
+
+
+def glipdemo_caption():
+    """A caption with one entity per phrase, and the character spans of the entities (what GLIPDemo's run_ner returns)."""
+    caption = "".join(n + " . " for n in GLIPDEMO_NAMES)
+    spans, pos = [], 0
+    for n in GLIPDEMO_NAMES:
+        spans.append([[pos, pos + len(n)]])
+        pos += len(n) + 3
+    return caption, spans
+
+
+def resize_box_case():
+    from mq_det_amd.structures import BoxList
+    g = torch.Generator().manual_seed(3)
+    xy = torch.rand(6, 2, generator=g) * 150
+    bl = BoxList(torch.cat([xy, xy + torch.rand(6, 2, generator=g) * 40], 1), (190, 150), mode="xyxy")
+    bl.add_field("scores", torch.rand(6, generator=g))
+    return bl, [{"orig_size": torch.tensor([300, 380]), "image_id": torch.tensor(7)}]
+
+
+def glipdemo_prediction_case():
+    from mq_det_amd.structures import BoxList
+    g = torch.Generator().manual_seed(4)
+    xy = torch.rand(20, 2, generator=g) * 150
+    bl = BoxList(torch.cat([xy, xy + torch.rand(20, 2, generator=g) * 40], 1), (190, 150), mode="xyxy")
+    bl.add_field("scores", torch.rand(20, generator=g) * 0.12)
+    bl.add_field("labels", torch.randint(1, 5, (20,), generator=g))
+    return bl
+
+
+@pytest.fixture(scope="module")
+def ref(golden_dir):
+    with open(os.path.join(golden_dir, "dropin_reference.json")) as f:
+        return json.load(f)
+
+
+def reference_cfg(ref, name):
+    """The reference's config tree `name` as recorded (tuples restored), in the same dict-based CfgNode oracle/_refload.py loads it into."""
+    from oracle._refload import CfgNode
+
+    def decode(v):
+        if isinstance(v, dict):
+            return tuple(decode(x) for x in v["__tuple__"]) if set(v) == {"__tuple__"} else CfgNode({k: decode(x) for k, x in v.items()})
+        if isinstance(v, list):
+            return [decode(x) for x in v]
+        return v
+    return decode(ref["cfg"][name])
+
+
+def reference_queries(ref, name):
+    """create_queries_and_maps_from_dataset's captions and label -> token positive maps, as recorded."""
+    q = ref["queries"][name]
+    return q["queries"], [{int(k): v for k, v in m.items()} for m in q["maps"]]
+
+
+def resize_box(output, targets):
+    """The caller's resize step (engine/inference.py resize_box): the one image's detections rescaled to targets[0]["orig_size"] = (h, w)."""
+    h, w = targets[0]["orig_size"].tolist()
+    return output.resize((w, h))
+
+
+def test_resize_box_matches_the_reference(ref):
+    bl, targets = resize_box_case()
+    r = resize_box(bl, targets)
+    assert list(r.size) == ref["resize_box"]["size"]
+    assert torch.allclose(r.bbox, torch.tensor(ref["resize_box"]["bbox"]), atol=1e-4)
+
+
+def test_reference_cfg_tree_and_caller_sequence(monkeypatch, ref):
     import ops_emulation as emu
-    from oracle import _refload, detector as od
+    from oracle import detector as od
     from oracle.spec import Spec
     from oracle.weights import make_state_dict, make_query_bank
     import mq_det_amd
@@ -44,13 +118,12 @@ def test_reference_cfg_tree_and_caller_sequence(monkeypatch):
     from mq_det_amd.utils.tokenizer import build_synthetic_tokenizer
 
     # ---- the reference's config tree, exactly as tools/test_grounding_net.py:100-106 builds it (cfg.merge_from_file x 2)
-    cfg = _refload.reference_cfg("configs/pretrain/mq-glip-t.yaml", "configs/vision_query_5shot/lvis_minival.yaml")
+    cfg = reference_cfg(ref, "mq-glip-t+lvis_minival")
     assert cfg.MODEL.META_ARCHITECTURE == "GeneralizedVLRCNN_New" and cfg.TEST.CHUNKED_EVALUATION == 40
     assert cfg.TEST.MDETR_STYLE_AGGREGATE_CLASS_NUM == 3000 and cfg.MODEL.ATSS.DETECTIONS_PER_IMG == 300
     # command-line style overrides (cfg.merge_from_list in the reference): a shallow model so that the CPU emulation is
     # quick, a local tokenizer directory (no network), no bank file (loaded through load_query_bank below)
-    words = [w for n in LVIS_LIKE for w in n.lower().replace("(", " ").replace(")", " ").replace("_", " ").split()]
-    tok_dir = build_synthetic_tokenizer(tempfile.mkdtemp(), size=4000, extra_words=words)
+    tok_dir = build_synthetic_tokenizer(tempfile.mkdtemp(), size=4000, extra_words=words_of(LVIS_LIKE))
     cfg.MODEL.SWINT.DEPTHS = (2, 2, 2, 2)
     cfg.MODEL.DYHEAD.NUM_CONVS = 2
     cfg.MODEL.LANGUAGE_BACKBONE.TOKENIZER_TYPE = tok_dir
@@ -78,13 +151,8 @@ def test_reference_cfg_tree_and_caller_sequence(monkeypatch):
     model.eval()
     model._validate_config()                                   # every key it reads exists in the reference tree; mq-glip-t passes
 
-    # ---- engine/inference.py: captions and positive maps from the reference's own builders
-    fns = _refload.reference_functions("maskrcnn_benchmark/engine/inference.py",
-                                       ["clean_name", "create_positive_dict", "chunks", "create_queries_and_maps",
-                                        "create_queries_and_maps_from_dataset", "resize_box"],
-                                       {"load_from_yaml_file": None})
-    dataset = types.SimpleNamespace(categories=lambda: {i + 1: n for i, n in enumerate(LVIS_LIKE)})
-    all_queries, all_maps = fns["create_queries_and_maps_from_dataset"](dataset, cfg, disable_print=True)
+    # ---- engine/inference.py: captions and positive maps from the reference's own builders (recorded, same category list and tokenizer)
+    all_queries, all_maps = reference_queries(ref, "glip_lvis_like")
     assert len(all_queries) == 2 and all_queries[0].startswith("aerosol can. air conditioner. airplane")
     assert sorted(all_maps[0]) == list(range(1, 41)) and sorted(all_maps[1]) == list(range(41, 51))
     bank = make_query_bank(range(1, 51), spec)
@@ -106,7 +174,7 @@ def test_reference_cfg_tree_and_caller_sequence(monkeypatch):
             output = model(images, captions=captions, positive_map=positive_map_label_to_token)
             output = [o.to(cpu_device) for o in output]
             output = output[0]
-            output = fns["resize_box"](output, targets)
+            output = resize_box(output, targets)
             scores = output.extra_fields["scores"]
             labels = output.extra_fields["labels"]
             boxes = output.bbox
@@ -123,7 +191,7 @@ def test_reference_cfg_tree_and_caller_sequence(monkeypatch):
         batched = model.forward_chunks(images, list(zip(all_queries, all_maps)))
     assert len(batched) == len(all_queries) and all(len(r) == 1 for r in batched)
     for res, (_, o) in zip(batched, mdetr_style_output):
-        r = fns["resize_box"](res[0].to(cpu_device), targets)
+        r = resize_box(res[0].to(cpu_device), targets)
         o1, o2 = torch.argsort(o["scores"], descending=True, stable=True), torch.argsort(r.extra_fields["scores"], descending=True, stable=True)
         assert len(o["scores"]) == len(r.extra_fields["scores"])
         assert torch.allclose(o["scores"][o1], r.extra_fields["scores"][o2], atol=1e-5)
@@ -144,14 +212,14 @@ def test_reference_cfg_tree_and_caller_sequence(monkeypatch):
     assert torch.allclose(ref["boxes"][o1] * 2.0, got["boxes"][o2], atol=2e-2)                    # resize_box: 150x190 -> 300x380
 
 
-def test_groundingdino_reference_cfg_and_caller_sequence(monkeypatch):
+def test_groundingdino_reference_cfg_and_caller_sequence(monkeypatch, ref):
     """The same evidence for the MQ-GroundingDINO family (BASELINE configs[4]): reference config tree = defaults.py +
     configs/pretrain/mq-groundingdino-t.yaml; `build_detection_model(cfg)` switches on `cfg.GROUNDINGDINO.enabled`
     (modeling/detector/__init__.py:9-11); strict load of a state_dict with the reference module's names; the eval loop body of
     engine/inference.py:599-643 on captions / positive maps from the reference's own builders; results vs the oracle (which is
     pinned to the reference's GroundingDINO module by tests/test_oracle_golden.py)."""
     import ops_emulation as emu
-    from oracle import _refload, gdino as og
+    from oracle import gdino as og
     from oracle.spec import tiny_gdino_spec
     from oracle.weights import make_gdino_state_dict, make_query_bank
     import mq_det_amd
@@ -160,12 +228,11 @@ def test_groundingdino_reference_cfg_and_caller_sequence(monkeypatch):
     from mq_det_amd.structures import to_image_list
     from mq_det_amd.utils.tokenizer import build_synthetic_tokenizer
 
-    cfg = _refload.reference_cfg("configs/pretrain/mq-groundingdino-t.yaml")
+    cfg = reference_cfg(ref, "mq-groundingdino-t")
     assert cfg.GROUNDINGDINO.enabled and cfg.GROUNDINGDINO.num_queries == 900 and cfg.GROUNDINGDINO.box_threshold == 0.05
     names = LVIS_LIKE[:12]
-    words = [w for n in names for w in n.lower().replace("(", " ").replace(")", " ").replace("_", " ").split()]
     spec = tiny_gdino_spec(vocab=4000)
-    tok_dir = build_synthetic_tokenizer(tempfile.mkdtemp(), size=spec.vocab, extra_words=words)
+    tok_dir = build_synthetic_tokenizer(tempfile.mkdtemp(), size=spec.vocab, extra_words=words_of(names))
     # command-line style overrides: shallow model (product-only keys for the depths the reference hard-codes by name), local tokenizer
     G = cfg.GROUNDINGDINO
     G.enc_layers, G.dec_layers, G.num_queries, G.text_encoder_type = spec.enc_layers, spec.dec_layers, spec.num_queries, tok_dir
@@ -190,12 +257,7 @@ def test_groundingdino_reference_cfg_and_caller_sequence(monkeypatch):
     model.load_state_dict(sd, strict=True)
     model.eval()
 
-    fns = _refload.reference_functions("maskrcnn_benchmark/engine/inference.py",
-                                       ["clean_name", "create_positive_dict", "chunks", "create_queries_and_maps",
-                                        "create_queries_and_maps_from_dataset", "resize_box"],
-                                       {"load_from_yaml_file": None})
-    dataset = types.SimpleNamespace(categories=lambda: {i + 1: n for i, n in enumerate(names)})
-    all_queries, all_maps = fns["create_queries_and_maps_from_dataset"](dataset, cfg, disable_print=True)
+    all_queries, all_maps = reference_queries(ref, "gdino_lvis_like12")        # the reference's builders on these names (recorded)
     assert len(all_queries) == 1 and sorted(all_maps[0]) == list(range(1, 13))
     bank = make_query_bank(range(1, 13), spec, seed=1, scales=1)
     model.load_query_bank(bank)
@@ -215,7 +277,7 @@ def test_groundingdino_reference_cfg_and_caller_sequence(monkeypatch):
         images.tensors.add_(0.0)                                   # an in-place write bumps the version counter: cache miss
         model(images, captions=[all_queries[0]], positive_map=all_maps[0])
         assert model.cache_stats["backbone_miss"] == 2
-        output = fns["resize_box"](output, targets)
+        output = resize_box(output, targets)
     scores, labels, boxes = output.extra_fields["scores"], output.extra_fields["labels"], output.bbox
     assert scores.dtype == torch.float32 and labels.dtype == torch.int64 and 0 < len(scores) <= spec.num_queries
     assert set(labels.tolist()) <= set(range(1, 13)) and float(scores.min()) > cfg.GROUNDINGDINO.box_threshold
@@ -240,17 +302,36 @@ def test_groundingdino_reference_cfg_and_caller_sequence(monkeypatch):
     assert sorted(qi) == [2, 5] and qi[2].shape == (1, 1, 256)
 
 
-def test_glipdemo_caller_sequence(monkeypatch):
-    """north_star: "keeping the GeneralizedVLRCNN / GLIPDemo API surface".  The reference's `GLIPDemo.compute_prediction`,
-    `_post_process_fixed_thresh` and `_post_process` (engine/predictor_glip.py:178-275) and its positive-map builders (:405-445)
-    are executed IN PLACE on the product model: category-list caption (" . " separators), `create_positive_map` from the
-    tokenizer's char_to_token, `plus = 1` label ids, `model(image_list, captions=[caption], positive_map=...)` with the default
-    (non-LVIS) score aggregation, `prediction.resize`, `has_field("mask")`, `predictions[keep]`, `.sort` -- results vs the oracle."""
-    import timeit
+def post_process(predictions, threshold):
+    """GLIPDemo's post-processing as a caller writes it on the BoxList API: keep scores above the threshold, `predictions[keep]`, then the
+    kept detections by descending score."""
+    keep = torch.nonzero(predictions.get_field("scores") > threshold).squeeze(1)
+    predictions = predictions[keep]
+    _, idx = predictions.get_field("scores").sort(0, descending=True)
+    return predictions[idx]
+
+
+def test_glipdemo_post_processing_matches_the_reference(ref):
+    pred = glipdemo_prediction_case()
+    top = post_process(pred, GLIPDEMO_THRESHOLD)
+    for key in ("post_process_fixed_thresh", "post_process"):
+        want = ref["glipdemo"][key]
+        assert top.get_field("labels").tolist() == want["labels"]
+        assert torch.allclose(top.get_field("scores"), torch.tensor(want["scores"]), atol=1e-6)
+        assert torch.allclose(top.bbox, torch.tensor(want["bbox"]), atol=1e-4)
+
+
+def test_glipdemo_caller_sequence(monkeypatch, ref):
+    """north_star: "keeping the GeneralizedVLRCNN / GLIPDemo API surface".  What the reference's `GLIPDemo.compute_prediction`
+    (engine/predictor_glip.py:178-238) hands to the model -- the category-list caption (" . " separators) and, from its positive-map builders
+    (:405-445, `create_positive_map` on the tokenizer's char_to_token, `plus = 1` label ids), the label -> token map -- is recorded in
+    tests/golden/dropin_reference.json; here the product model takes that call, `model(image_list, captions=[caption], positive_map=...)` with
+    the default (non-LVIS) score aggregation, then `prediction.resize`, `has_field("mask")`, `predictions[keep]`, `.sort` (the post-processing
+    of :240-275, pinned by test_glipdemo_post_processing_matches_the_reference) -- results vs the oracle."""
     import numpy as np
     import ops_emulation as emu
     from transformers import AutoTokenizer
-    from oracle import _refload, detector as od
+    from oracle import detector as od
     from oracle.spec import Spec
     from oracle.weights import make_state_dict
     import mq_det_amd
@@ -259,8 +340,8 @@ def test_glipdemo_caller_sequence(monkeypatch):
     from mq_det_amd.structures import to_image_list
     from mq_det_amd.utils.tokenizer import build_synthetic_tokenizer
 
-    names = ["person", "sports ball", "traffic light", "dog"]
-    cfg = _refload.reference_cfg("configs/pretrain/mq-glip-t.yaml")
+    names = GLIPDEMO_NAMES
+    cfg = reference_cfg(ref, "mq-glip-t")
     assert cfg.TEST.MDETR_STYLE_AGGREGATE_CLASS_NUM == -1 and cfg.MODEL.RPN_ARCHITECTURE == "VLDYHEAD"
     tok_dir = build_synthetic_tokenizer(tempfile.mkdtemp(), size=4000, extra_words=[w for n in names for w in n.split()])
     cfg.MODEL.SWINT.DEPTHS, cfg.MODEL.DYHEAD.NUM_CONVS = (2, 2, 2, 2), 2
@@ -279,48 +360,50 @@ def test_glipdemo_caller_sequence(monkeypatch):
         return self._plan
     monkeypatch.setattr(detector.GeneralizedVLRCNN_New, "prepare", prepare)
 
-    ref = _refload.reference_classes("maskrcnn_benchmark/engine/predictor_glip.py", ["GLIPDemo"],
-                                     ["create_positive_map", "create_positive_map_label_to_token_from_positive_map"],
-                                     {"to_image_list": to_image_list, "timeit": timeit, "print": lambda *a, **k: None})
-    demo = ref["GLIPDemo"].__new__(ref["GLIPDemo"])            # GLIPDemo.__init__ minus checkpoint / cv2 / nltk plumbing (:29-61)
-    demo.cfg = cfg
-    demo.model = mq_det_amd.build_detection_model(cfg)
-    demo.model.load_state_dict(sd, strict=True)
-    demo.model.eval()
-    demo.device = demo.cpu_device = torch.device("cpu")
-    demo.tokenizer = AutoTokenizer.from_pretrained(tok_dir)     # build_tokenizer (:93-106)
+    model = mq_det_amd.build_detection_model(cfg)
+    model.load_state_dict(sd, strict=True)
+    model.eval()
+    tokenizer = AutoTokenizer.from_pretrained(tok_dir)         # build_tokenizer (:93-106)
     mean, std = torch.tensor(cfg.INPUT.PIXEL_MEAN).view(3, 1, 1), torch.tensor(cfg.INPUT.PIXEL_STD).view(3, 1, 1)
-    demo.transforms = lambda img: (torch.from_numpy(img).permute(2, 0, 1).float() - mean) / std     # build_transform without the resize
-    demo.confidence_threshold = 0.06
+    transforms = lambda img: (torch.from_numpy(img).permute(2, 0, 1).float() - mean) / std     # noqa: E731 -- build_transform without the resize
     g = np.random.default_rng(0)
     image = (g.random((150, 190, 3)) * 255).astype(np.float32)
+    demo = ref["glipdemo"]
+    assert demo["plus"] == 1 and len(demo["calls"]) == 2
+
+    def compute_prediction(call):
+        """The model call of compute_prediction with the recorded caption / map, then the resize to the original image and the mask check."""
+        caption, pm = call["captions"][0], {int(k): v for k, v in call["positive_map"].items()}
+        image_list = to_image_list(transforms(image), cfg.DATALOADER.SIZE_DIVISIBILITY).to(torch.device("cpu"))
+        with torch.no_grad():
+            predictions = [o.to(torch.device("cpu")) for o in model(image_list, captions=[caption], positive_map=pm)]
+        height, width = image.shape[:-1]
+        return predictions[0].resize((width, height)), caption, pm
 
     # (a) a list of category names: the reference joins them with " . " and wraps ALL spans into ONE entity (:185-196), i.e. a
     # single label whose score is the mean over every token of the caption
-    pred = demo.compute_prediction(image, names)
-    assert demo.plus == 1 and sorted(demo.positive_map_label_to_token) == [1] and len(demo.positive_map_label_to_token[1]) == 6
+    pred, caption, pm = compute_prediction(demo["calls"][0])
+    assert caption == "".join(n + " . " for n in names)
+    assert sorted(pm) == [1] and len(pm[1]) == 6
     assert set(pred.get_field("labels").tolist()) <= {1}
     # (b) a caption string with one entity per phrase (`run_ner` = nltk noun phrases in the reference; here: the spans directly)
-    caption = "".join(n + " . " for n in names)
-    spans, pos = [], 0
-    for n in names:
-        spans.append([[pos, pos + len(n)]])
-        pos += len(n) + 3
-    demo.run_ner = lambda text: spans
-    pred = demo.compute_prediction(image, caption)
-    assert sorted(demo.positive_map_label_to_token) == [1, 2, 3, 4]
+    pred, caption, pm = compute_prediction(demo["calls"][1])
+    assert caption == glipdemo_caption()[0]
+    assert sorted(pm) == [1, 2, 3, 4]
+    t = tokenizer([caption], return_tensors="pt")
+    for label, ((c0, c1),) in zip(sorted(pm), glipdemo_caption()[1]):      # each label's tokens are the tokens of its span
+        assert pm[label] == sorted({t.char_to_token(0, c) for c in range(c0, c1) if t.char_to_token(0, c) is not None})
     assert pred.size == (190, 150) and not pred.has_field("mask")
-    top = demo._post_process_fixed_thresh(pred)
-    top2 = demo._post_process(pred, threshold=0.06)
-    assert len(top) == len(top2) > 0 and bool((top.get_field("scores")[:-1] >= top.get_field("scores")[1:]).all())
-    assert float(top.get_field("scores").min()) > 0.06 and set(top.get_field("labels").tolist()) <= {1, 2, 3, 4}
+    top = post_process(pred, GLIPDEMO_THRESHOLD)
+    assert len(top) > 0 and bool((top.get_field("scores")[:-1] >= top.get_field("scores")[1:]).all())
+    assert float(top.get_field("scores").min()) > GLIPDEMO_THRESHOLD and set(top.get_field("labels").tolist()) <= {1, 2, 3, 4}
 
     # oracle on the same pixels / caption / label map
-    t = demo.tokenizer([caption], max_length=256, padding="max_length", return_special_tokens_mask=True, return_tensors="pt", truncation=True)
-    pimg, sizes = od.pad_images([demo.transforms(image)], cfg.DATALOADER.SIZE_DIVISIBILITY)
+    t = tokenizer([caption], max_length=256, padding="max_length", return_special_tokens_mask=True, return_tensors="pt", truncation=True)
+    pimg, sizes = od.pad_images([transforms(image)], cfg.DATALOADER.SIZE_DIVISIBILITY)
     with torch.no_grad():
-        dets = od.forward(sd, spec, pimg, sizes, t["input_ids"], t["attention_mask"], dict(demo.positive_map_label_to_token), None)
-    keep = dets[0]["scores"] > 0.06
+        dets = od.forward(sd, spec, pimg, sizes, t["input_ids"], t["attention_mask"], dict(pm), None)
+    keep = dets[0]["scores"] > GLIPDEMO_THRESHOLD
     o1 = torch.argsort(dets[0]["scores"][keep], descending=True, stable=True)
     assert int(keep.sum()) == len(top)
     assert torch.allclose(dets[0]["scores"][keep][o1], top.get_field("scores"), atol=2e-4)

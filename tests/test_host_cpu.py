@@ -1,5 +1,6 @@
 """CPU tests: C-ABI library loads and exports every symbol include/mqdet_hip.h declares (no compute calls),
 boundary containers, config, tokenizer glue, state_dict naming contract, fail-loud behaviour without a GPU."""
+import json
 import os
 import re
 import subprocess
@@ -302,6 +303,9 @@ def test_bench_gpus_flag_starts_the_ranks():
     import json
     bench = os.path.join(ROOT, "bench.py")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    # no GPU visible to the ranks, also on a GPU box: the launcher check runs on the CPU over gloo (with GPUs visible it would take
+    # RCCL and need one GPU per rank)
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, bench, "--gpus", "2", "--dry-launch", "--steps", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -325,10 +329,10 @@ def test_bench_gpus_flag_starts_the_ranks():
     assert r.returncode != 0 and "refusing" in r.stderr and "{" not in r.stdout
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="compares with reference code executed in place")
 def test_gloo_world2_evaluator_gather_matches_reference():
     """per-category top-k accumulation + cross-rank gather as tensors == the reference's LvisEvaluatorFixedAP
-    (update / _merge_lists / synchronize_between_processes over its pickling all_gather), 2 gloo processes."""
+    (update / _merge_lists / synchronize_between_processes over its pickling all_gather, recorded by oracle/gen_golden_dropin.py in
+    tests/golden/dropin_reference.json), 2 gloo processes."""
     script = os.path.join(ROOT, "tests", "_gloo_eval_worker.py")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
@@ -338,18 +342,9 @@ def test_gloo_world2_evaluator_gather_matches_reference():
     assert r.stdout.count("EVAL_GATHER_OK") == 2
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="compares with reference code executed in place")
-def test_evaluator_update_boxlist_matches_reference_prepare():
-    """ADVICE r2: a detection handed over as a BoxList must reach the LVIS API with the bbox `LvisEvaluatorFixedAP.prepare` builds
-    (lvis_eval.py:810-835 via convert_to_xywh :998-1000: no legacy +1), from the (image id, dict) pairs of engine/inference.py:643-648."""
+def evaluator_update_preds():
+    """(image id, dict) pairs as engine/inference.py:643-648 hands them to the evaluator: three images of 9 detections, one empty."""
     import torch
-    from mq_det_amd.evaluation import FixedAPAccumulator
-    from mq_det_amd.structures import BoxList
-    from oracle import _refload
-    ev = _refload.reference_classes("maskrcnn_benchmark/data/datasets/evaluation/lvis/lvis_eval.py", ["LvisEvaluatorFixedAP"],
-                                    ["_merge_lists", "convert_to_xywh"], {"LVIS": object})
-    ref = ev["LvisEvaluatorFixedAP"](gt=None, topk=50)
-    acc = FixedAPAccumulator(topk=50)
     g = torch.Generator().manual_seed(5)
     preds = []
     for img in (11, 12, 13):
@@ -359,21 +354,29 @@ def test_evaluator_update_boxlist_matches_reference_prepare():
         boxes = torch.cat([xy, xy + wh], 1)
         labels, scores = torch.randint(1, 4, (n,), generator=g), torch.rand(n, generator=g)
         preds.append((img, {"scores": scores, "labels": labels, "boxes": boxes}))
-        bl = BoxList(boxes, (640, 480), mode="xyxy")
-        bl.add_field("scores", scores)
-        bl.add_field("labels", labels)
-        acc.update_boxlist(img, bl)
     preds.append((14, {"scores": torch.zeros(0), "labels": torch.zeros(0, dtype=torch.long), "boxes": torch.zeros(0, 4)}))
-    empty = BoxList(torch.zeros(0, 4), (640, 480), mode="xyxy")
-    empty.add_field("scores", torch.zeros(0))
-    empty.add_field("labels", torch.zeros(0, dtype=torch.long))
-    acc.update_boxlist(14, empty)
-    ref.update(preds)                                     # update() -> prepare() -> convert_to_xywh
+    return preds
+
+
+def test_evaluator_update_boxlist_matches_reference_prepare():
+    """ADVICE r2: a detection handed over as a BoxList must reach the LVIS API with the bbox `LvisEvaluatorFixedAP.prepare` builds
+    (lvis_eval.py:810-835 via convert_to_xywh :998-1000: no legacy +1), from the (image id, dict) pairs of engine/inference.py:643-648.
+    The reference evaluator's by_cat after update() of these pairs is recorded in tests/golden/dropin_reference.json (oracle/gen_golden_dropin.py)."""
+    from mq_det_amd.evaluation import FixedAPAccumulator
+    from mq_det_amd.structures import BoxList
+    with open(os.path.join(ROOT, "tests", "golden", "dropin_reference.json")) as f:
+        ref_by_cat = json.load(f)["evaluator"]["update_topk50"]
+    acc = FixedAPAccumulator(topk=50)
+    for img, p in evaluator_update_preds():
+        bl = BoxList(p["boxes"], (640, 480), mode="xyxy")
+        bl.add_field("scores", p["scores"])
+        bl.add_field("labels", p["labels"])
+        acc.update_boxlist(img, bl)
     mine = acc.by_cat()
-    assert set(mine) == set(ref.by_cat)
-    for cat, anns in ref.by_cat.items():
-        a = sorted((x["image_id"], round(x["score"], 6), tuple(round(v, 4) for v in x["bbox"])) for x in anns)
-        b = sorted((x["image_id"], round(x["score"], 6), tuple(round(v, 4) for v in x["bbox"])) for x in mine[cat])
+    assert set(mine) == {int(c) for c in ref_by_cat}
+    for cat, anns in ref_by_cat.items():
+        a = sorted((i, round(s, 6), tuple(round(v, 4) for v in b)) for i, s, b in anns)
+        b = sorted((x["image_id"], round(x["score"], 6), tuple(round(v, 4) for v in x["bbox"])) for x in mine[int(cat)])
         assert a == b, (cat, a[:2], b[:2])
 
 
