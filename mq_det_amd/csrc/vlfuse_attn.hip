@@ -532,10 +532,13 @@ namespace { constexpr int WS_LD = VD + 4; }               // 260 floats: rows st
 // TDMA (round 6, 16-bit builds): the key / value tiles go global -> LDS by LDS-DMA (`buffer_load ... lds`, csrc/common.h) instead of through a
 // register ring: no tile registers, no ds_write, no register wait in front of the commit.  The tile rows are PADDED in LDS (pitch 272 halfs), a
 // copy piece is 1 KB of consecutive LDS bytes: lane l of piece c writes LDS chunk g = 64 c + l, i.e. (row g / 34, position g % 34) -- positions
-// 32, 33 are the padding (they fetch the row's chunk 0; nobody reads them).  Rows past the image come back as zeros (buffer range check; the
-// keys are masked by position anyway).  Tile pos + 1 is requested at the top of step pos into the buffer step pos - 1 read, and has the whole
-// step to land.  The two buffers are handed to the loop as __restrict__ pointers (vl_scoped_tiles): without alias scopes hipcc makes every
-// LDS read behind the copy wait for it.
+// 32, 33 are the padding (they fetch the row's chunk 0; nobody reads them).  Rows past the image come back as zeros: the descriptor covers
+// the image's N rows and the tile offset goes in the VECTOR offset with the lane's -- the range check of a raw buffer compares voffset +
+// inst_offset with num_records and leaves soffset out, so a tile offset in soffset would read up to 63 rows past the image (the next
+// image's, or past the end of v_ln for the last one) into the value operand, where 0 x NaN is NaN.  (The keys are masked by position.)
+// Tile pos + 1 is requested at the top of step pos into the buffer step pos - 1 read, and has the whole step to land.  The two buffers are
+// handed to the loop as __restrict__ pointers (vl_scoped_tiles): without alias scopes hipcc makes every LDS read behind the copy wait for it
+// (DESIGN.md section 20).
 template <class T, class F>
 __device__ __forceinline__ void vl_scoped_tiles(T* __restrict__ b0, T* __restrict__ b1, F f) { f(b0, b1); }
 
@@ -610,11 +613,11 @@ __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_t2i_kernel(T2IParams p
   const mq_rsrc v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, p.N * VD * (int)sizeof(half_t), 0x00020000);
   auto dma_tile = [&](int pos, half_t* buf) __attribute__((always_inline)) {
     const int t = t0 + min(pos, max(nt - 1, 0));
-    const int soff = __builtin_amdgcn_readfirstlane(t * TK * VD * (int)sizeof(half_t));
+    const int toff = __builtin_amdgcn_readfirstlane(t * TK * VD * (int)sizeof(half_t));     // range-checked: voffset, not soffset
 #pragma unroll
     for (int i = 0; i < PR; ++i) {
       const int piece = wv + i * NWV;
-      if (piece < NPC) lds_stage_16b_buf(v_rsrc, soff, leoff[i], buf + piece * 512);
+      if (piece < NPC) lds_stage_16b_buf(v_rsrc, 0, toff + leoff[i], buf + piece * 512);
     }
   };
   if constexpr (ABL != 0) {

@@ -880,7 +880,7 @@ def conv3x3_nchw32_group(levels, w_packed, bias, n_out):
         Bx, H, W, Cx = x.shape
         assert Bx == B and Cx == C and x.dtype == levels[0].dtype and x.stride(3) == 1 and x.stride(2) == C and x.stride(1) == W * C
         out = torch.empty(B, n_out, H, W, dtype=torch.float32, device=x.device)
-        a.x, a.out, a.x_bs, a.H, a.W = x.data_ptr(), out.data_ptr(), x.stride(0), H, W
+        a.x, a.out, a.x_bs, a.H, a.W = _ptr(x).value, _ptr(out).value, x.stride(0), H, W
         outs.append(out)
         nbytes += B * H * W * C * 2 + out.numel() * 4
     with _timed("conv3x3_group", nbytes):
@@ -1015,10 +1015,8 @@ def dcnv2_group(branches, want_stats=True, tag="dcnv2_fused", ablation=0):
                 assert wy.dtype == wx.dtype == torch.float32 and wy.numel() == Ho and wx.numel() == Wo
         w, wflag = _dcn_w(w)
         keep.append(w)
-        a.x, a.om, a.w, a.bias, a.out = x.data_ptr(), om.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr()
-        a.stats = sums.data_ptr() if sums is not None else None
-        a.wy = wy.data_ptr() if wy is not None else None
-        a.wx = wx.data_ptr() if wx is not None else None
+        a.x, a.om, a.w, a.bias, a.out = _ptr(x).value, _ptr(om).value, _ptr(w).value, _ptr(bias).value, _ptr(y).value
+        a.stats, a.wy, a.wx = _ptr(sums).value, _ptr(wy).value, _ptr(wx).value
         a.x_bs, a.B, a.H, a.W, a.C, a.oH, a.oW = x.stride(0), B, H, W, C, om.shape[2], om.shape[3]
         a.N, a.out_ld, a.stride, a.flags = 256, 256, stride, (int(bool(br.get("mask_prob", False))) | (2 if br.get("plain", False) else 0) | wflag
                                                              | ((int(ablation) & 15) << 8 if i == 0 else 0))
@@ -1068,7 +1066,7 @@ def dyconv_coef_group(items, attn_w, attn_b, groups, eps):
         assert sums.dtype == torch.float32 and sums.is_contiguous() and sums.shape[2:] == (256, 3)
         B, C = sums.shape[0], sums.shape[2]
         coef = torch.empty(B, C, 2, dtype=torch.float32, device=sums.device)
-        a.sums, a.gamma, a.beta, a.coef = sums.data_ptr(), it["gamma"].data_ptr(), it["beta"].data_ptr(), coef.data_ptr()
+        a.sums, a.gamma, a.beta, a.coef = _ptr(sums).value, _ptr(it["gamma"]).value, _ptr(it["beta"]).value, _ptr(coef).value
         a.nblk, a.n, a.nbranches, a.reserved = sums.shape[1], int(it["n"]), int(it["nbranches"]), 0
         outs.append(coef)
     _chk(_fn(lib, "mq_dyconv_coef_group", *[it["gamma"] for it in items])(ctypes.cast(arr, _vp), len(items), _ptr(attn_w), _ptr(attn_b), B, C, groups, float(eps), _stream()),
@@ -1126,10 +1124,10 @@ def dyconv_epilogue_group(levels, w0, b0, w2, b2, relu_coef):
         for k, (y, cf, hs, ws) in enumerate(branches):
             _need_gpu(y, cf)
             assert y.is_contiguous() and cf.is_contiguous() and y.shape == (B, hs * ws, C) and y.dtype == y0.dtype and cf.dtype == torch.float32
-            a.y[k], a.coef[k], a.hs[k], a.ws[k] = y.data_ptr(), cf.data_ptr(), hs, ws
+            a.y[k], a.coef[k], a.hs[k], a.ws[k] = _ptr(y).value, _ptr(cf).value, hs, ws
             nbytes += y.numel() * 2
         a.nbranches, a.H, a.W, a.reserved = len(branches), H, W, 0
-        a.out, a.out_bs, a.pool, a.relu_coef = out.data_ptr(), out.stride(0), pool.data_ptr(), relu_coef[l].data_ptr()
+        a.out, a.out_bs, a.pool, a.relu_coef = _ptr(out).value, out.stride(0), _ptr(pool).value, _ptr(relu_coef[l]).value
         nbytes += B * H * W * C * 2
     with _timed("dyconv_epilogue_group", nbytes):
         _chk(_fn(lib, "mq_dyconv_epilogue_group", y0)(ctypes.cast(arr, _vp), len(levels), _ptr(w0), _ptr(b0), _ptr(w2), _ptr(b2), B, C, _stream()),
@@ -1204,7 +1202,7 @@ def pool2x2_tokens(feats):
         x = f.permute(0, 2, 3, 1)
         Bx, H, W, Cx = x.shape
         assert Bx == B and Cx == C and x.dtype == feats[0].dtype and x.stride(3) == 1 and x.stride(2) == C and x.stride(1) == W * C and H >= 2 and W >= 2
-        a.x, a.out, a.x_bs, a.H, a.W = x.data_ptr(), None, x.stride(0), H, W
+        a.x, a.out, a.x_bs, a.H, a.W = _ptr(x).value, None, x.stride(0), H, W
         n += (H // 2) * (W // 2)
     out = torch.empty(B, n, C, dtype=feats[0].dtype, device=feats[0].device)
     with _timed("pool2x2_tokens", sum(f.numel() for f in feats) * 2 + out.numel() * 2):
@@ -1340,7 +1338,7 @@ def post_select(ranked, reg, anchors, ks, label_ids, im_wh):
     scores = torch.empty(B, tot, dtype=torch.float32, device=dev)
     labels = torch.empty(B, tot, dtype=torch.int32, device=dev)
     ids = torch.empty(B, tot, dtype=torch.int32, device=dev)
-    pp = lambda ts: (ctypes.c_void_p * NL)(*[t.data_ptr() for t in ts])      # noqa: E731  host arrays of device pointers
+    pp = lambda ts: (ctypes.c_void_p * NL)(*[_ptr(t).value for t in ts])      # noqa: E731  host arrays of device pointers
     hw = (ctypes.c_int * NL)(*[int(r.shape[1]) for r in ranked])
     kk = (ctypes.c_int * NL)(*[int(k) for k in ks])
     wsb = lib.mq_post_select_workspace_bytes(ctypes.cast(hw, _vp), ctypes.cast(kk, _vp), NL, B, L)

@@ -86,8 +86,8 @@ def pointer_guard(mode="end"):
     """Inside: every tensor handed to the library through mq_det_amd.ops._ptr is replaced, for the duration of the call, by a copy of
     its WHOLE storage placed against a guard page (views keep their offset inside it), and copied back afterwards (outputs).  The
     parity checks run unchanged; a kernel that touches a byte outside the storage of any of its arguments on the guarded side
-    kills the process with SIGSEGV (run it in a subprocess).  Pointers inside ctypes structs (the grouped DCNv2 / coefficient launches)
-    bypass _ptr and are not guarded."""
+    kills the process with SIGSEGV (run it in a subprocess).  The pointers the grouped launches pass inside ctypes structs are taken
+    through _ptr as well, so they are guarded too."""
     from mq_det_amd import ops
     live = {}                                             # storage data_ptr -> (uint8 view of the original storage, guarded uint8 copy)
 

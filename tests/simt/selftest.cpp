@@ -77,3 +77,17 @@ extern "C" int simt_selftest_deadlock(int* out) {
   hipLaunchKernelGGL(st_deadlock_kernel, dim3(1), dim3(64), 0, nullptr, out);
   return hipGetLastError();
 }
+
+// one raw-buffer LDS copy (16 bytes per lane) over a descriptor of num_records bytes at `base`, every lane with the same voffset / soffset:
+// out[l] = the 16 bytes lane l received.  The range check covers voffset + inst_offset only (soffset is not checked).
+__global__ void st_buffer_lds_kernel(const void* base, int num_records, int voff, int soff, unsigned char* out) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[64 * 16];
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, num_records, 0x00020000);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
+  __syncthreads();
+  for (int j = 0; j < 16; ++j) out[threadIdx.x * 16 + j] = lds[threadIdx.x * 16 + j];
+}
+extern "C" int simt_selftest_buffer_lds(const void* base, int num_records, int voff, int soff, unsigned char* out) {
+  hipLaunchKernelGGL(st_buffer_lds_kernel, dim3(1), dim3(64), 0, nullptr, base, num_records, voff, soff, out);
+  return hipGetLastError();
+}

@@ -112,6 +112,29 @@ def test_emulation_unit_kernels():
     assert lib.simt_selftest_deadlock(vp(o.data_ptr())) != 0   # hipErrorLaunchFailure instead of a hang
 
 
+def test_emulation_buffer_range_check_ignores_soffset():
+    """The raw-buffer LDS copy as the hardware range-checks it: voffset + inst_offset against num_records, soffset added to the address but
+    not checked.  A 64-byte descriptor over a larger host array: soffset 4096 still reads base + 4096, voffset 64 reads zeros."""
+    import ctypes
+    import simt
+    lib = simt.library()
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    host = torch.arange(8192, dtype=torch.int32).to(torch.uint8)
+    out = torch.full((64, 16), 0xAB, dtype=torch.uint8)
+
+    def load(voff, soff):
+        out.fill_(0xAB)
+        assert lib.simt_selftest_buffer_lds(vp(host.data_ptr()), ci(64), ci(voff), ci(soff), vp(out.data_ptr())) == 0
+        return out.clone()
+
+    assert torch.equal(load(0, 0), host[0:16].expand(64, 16))
+    assert torch.equal(load(48, 0), host[48:64].expand(64, 16))          # the last 16 bytes inside the range
+    assert torch.equal(load(0, 4096), host[4096:4112].expand(64, 16))    # soffset: not checked
+    assert torch.equal(load(48, 4096), host[4144:4160].expand(64, 16))
+    assert not load(64, 0).any()                                          # voffset past num_records: zeros
+    assert not load(4096, 0).any()
+
+
 @pytest.mark.parametrize("schedule,names", [
     (("descending", 0), ("check_attention_strided", "check_window_attention", "check_gcp_block", "check_layernorm", "check_swin_mlp",
                          "check_nms", "check_post_golden", "check_msdeform_attn")),
@@ -529,22 +552,86 @@ OPT_IN = {"MQ_ATTN_RESIDENT": "1", "MQ_LN_VARIANT": "2", "MQ_OFFSET_CONV_VARIANT
           "MQ_NMS_EARLY_STOP": "1"}
 
 
+# the default cross-section: the VLFuse checks (every QUICK case has a ragged last key tile), and checks that reach the launchers passing
+# their pointers inside ctypes structs (grouped DCNv2, the grouped 3x3 conv, DyConv coefficients / epilogue, the pooled FPN tokens)
+OOB_NAMES = ["attention_small", "check_layernorm", "check_window_attention", "check_conv3x3", "check_bert_attn_qkv", "check_gcp_attn_fused",
+             "check_vlfuse_kernels", "check_vlfuse_heads_mask", "check_dcn", "check_dyconv", "check_swin_fpn", "pooled_tokens"]
+OOB_NAMES_FULL = ["check_gcp_block", "check_pre_select", "check_vl_fuse", "check_post_golden", "check_score_agg", "check_nms", "check_swin_mlp",
+                  "check_roi_align", "check_msdeform_attn", "check_attention_qk_mask", "check_msdeform_attn_q", "check_attention_strided"]
+
+
 @pytest.mark.parametrize("mode", ["end", "start"])
 def test_no_kernel_touches_memory_outside_its_buffers(mode):
     """Inputs, outputs and workspaces of every call sit directly against a PROT_NONE page (after them: mode "end", before: "start"); one
     byte too far is a SIGSEGV.  Shipped kernels on a cross-section of checks, and the opt-in kernels of section 12 (which have never
     run on a device, where such an access is a silent wrong read or a memory fault that takes the process down)."""
-    names = ["attention_small", "check_layernorm", "check_window_attention", "check_conv3x3", "check_bert_attn_qkv", "check_gcp_attn_fused"]      # (all 20 check groups pass: MQ_SIMT_FULL=1)
+    names = list(OOB_NAMES)                      # (all 20 check groups pass: MQ_SIMT_FULL=1)
     if os.environ.get("MQ_SIMT_FULL", "0") == "1":
-        names += ["check_gcp_block", "check_pre_select", "check_vlfuse_kernels", "check_vl_fuse", "check_dcn", "check_dyconv", "check_post_golden",
-                  "check_score_agg", "check_nms", "check_swin_mlp", "check_roi_align", "check_msdeform_attn", "check_swin_fpn", "check_attention_qk_mask",
-                  "check_msdeform_attn_q", "check_attention_strided"]
+        names += OOB_NAMES_FULL
     rc, lines, err = _oob(mode, names)
     assert rc == 0 and lines == ["OK " + n for n in names], (rc, lines, err)
     names = ["attention_small", "check_attention_strided", "check_layernorm", "check_pre_select", "check_conv3x3", "check_swin_fpn",
              "check_attention_qk_mask", "check_post_golden"]
     rc, lines, err = _oob(mode, names, OPT_IN)
     assert rc == 0 and lines == ["OK " + n for n in names], (rc, lines, err)
+
+
+def test_vlfuse_text_side_reads_nothing_past_the_last_image(tmp_path):
+    """VLFuse text side with v_ln at the very end of its memory (tests/vlfuse_tail.py): against a guard page, and followed by NaN, on the
+    LDS-DMA staging (MQ_VL_T2I_DMA=1, the default) and the register ring (=0) -- N = 1 .. 1000 with ragged last tiles, 1 and 3 images,
+    4 and 8 heads, 1 - 3 key splits (empty ones included), with and without an image key mask, against a float64 softmax(q k^T) v.  A key /
+    value tile that reads rows past the image gets SIGSEGV or NaN (0 x NaN in the PV product).  The two stagings give the same bits."""
+    import subprocess
+    import simt
+    simt.build_emu.build()                          # once, here: the four processes below only load it
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = {}
+    for follow in ("guard", "nan"):
+        for dma in ("1", "0"):
+            out = str(tmp_path / f"{follow}_{dma}.pt")
+            runs[(follow, dma)] = (out, subprocess.Popen([sys.executable, os.path.join(root, "tests", "vlfuse_tail.py"), "cpu", follow, "cpu", out],
+                                                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                                                         env=dict(os.environ, MQ_VL_T2I_DMA=dma)))
+    fails = []
+    for key, (out, p) in runs.items():
+        text, _ = p.communicate(timeout=1500)
+        if p.returncode != 0:
+            fails.append(f"{key}: rc {p.returncode}\n" + "\n".join(ln for ln in text.splitlines() if not ln.startswith("OK"))[-1500:])
+    assert not fails, "\n".join(fails)
+    for follow in ("guard", "nan"):
+        a, b = torch.load(runs[(follow, "1")][0]), torch.load(runs[(follow, "0")][0])
+        assert a.keys() == b.keys() and len(a) == 48
+        assert all(torch.equal(a[k], b[k]) for k in a), [k for k in a if not torch.equal(a[k], b[k])][:3]
+
+
+@pytest.mark.parametrize("fill", ["nan", "big"])
+def test_no_kernel_reads_or_writes_the_poison_halos(fill):
+    """The same cross-section with every library argument between two 64 KiB poison halos (tests/halo.py -- the harness the device suite
+    uses): NaN / +65504 halos leave every parity row passing (no read past an argument reaches a result) and every halo intact (no write)."""
+    rc, lines, err = _oob("halo-" + fill, OOB_NAMES)
+    assert rc == 0 and lines == ["OK " + n for n in OOB_NAMES], (rc, lines, err)
+
+
+def test_poison_halos_do_catch_an_overrun():
+    """negative control: mq_layernorm_fwd told about one row more than its output holds writes into that output's end halo -- reported by
+    entry point, argument, side and offset; the same call with the right row count passes"""
+    import ctypes
+    import simt
+    from mq_det_amd import ops
+    from halo import poisoned_args
+    x = torch.randn(65, 256).half()
+    w = torch.ones(256).half()
+    vp = ctypes.c_void_p
+    with simt.installed(), poisoned_args("nan"):
+        for rows in (64, 65):
+            y = torch.zeros(64, 256, dtype=torch.float16)
+            rc = ops._LIB.mq_layernorm_fwd(ops._ptr(x), 0, vp(0), 0, ops._ptr(w), ops._ptr(w), ops._ptr(y), vp(0), vp(0), rows, 256, 1e-5, vp(0))
+            if rows == 64:
+                ops._chk(rc, "mq_layernorm_fwd")
+                assert torch.isfinite(y).all() and y.abs().sum() > 0          # the result came back from the copy
+            else:
+                with pytest.raises(AssertionError, match=r"mq_layernorm_fwd: argument 'y' .*the end halo was written \(1 bytes after its last byte"):
+                    ops._chk(rc, "mq_layernorm_fwd")
 
 
 def test_guard_pages_do_catch_an_overrun():
