@@ -442,6 +442,34 @@ int mq_post_sort_fwd(const float* boxes, const float* scores, const int* labels,
 int mq_post_finalize_fwd(const float* boxes, const float* scores, const int* labels, const unsigned char* keep, float* out,
                          int* counts, int B, int tot, int K, int K2, void* stream);
 
+/* ---- Test-time augmentation (TEST.USE_MULTISCALE; csrc/tta.hip, host side mq_det_amd/tta.py).  uint8 / fp32 / integer data only.
+ * mq_tta_ingest_fwd: B ragged RGB uint8 HWC images (image b at src + src_off[b]) -> out [B, 3, Hp, Wp] fp32 and, when out_flip is not NULL,
+ *   the horizontally flipped canvas in out_flip (same shape), zero-padded; bit-exact to PIL's uint8 BILINEAR resize.  meta [B, 16] int32
+ *   (H_in, W_in, H_out, W_out, x-table offset, x-coefficient offset, x taps, y-table offset, y-coefficient offset, y taps, 0...), bounds
+ *   [*, 2] int32 (first input index, taps) per output column / row, coef int32 22-bit fixed-point weights; TH output rows per workgroup,
+ *   R = largest input-row window of a tile (LDS R * 192 bytes <= 160 KB); mean / stdv HOST float[3]; bgr: channels reversed; x255: x 255
+ *   before the normalisation; err [1] int32 (zeroed by the caller) is set
+ *   when a tile needs more than R input rows (tables that do not match R).  -1: sizes out of range.
+ * Replaces box_aug.py:65-127 (im_detect_bbox / im_detect_bbox_hflip: T.Resize -> T.RandomHorizontalFlip(1.0) -> T.ToTensor -> T.Normalize
+ *   -> to_image_list), data/transforms/transforms.py:84-175, structures/image_list.py:29-70. */
+int mq_tta_ingest_fwd(const unsigned char* src, const long* src_off, const int* meta, const int* bounds, const int* coef, float* out,
+                      float* out_flip, int* err, int B, int Hp, int Wp, int TH, int R, const float* mean, const float* stdv, int bgr, int x255,
+                      void* stream);
+/* mq_tta_merge_prep: packed [T, B, K, 6] fp32 detections of T transforms + counts [T, B] int32 -> per row: un-flip (tparam [T, B, 4]:
+ *   scaled width when flipped else -1, width ratio, height ratio, -), area band (band [T, 2] squared (min, max) or NULL), rescale, class
+ *   filter (cls_rank [n_cls] int32: position of the label in the class list, -1 = dropped), then the surviving rows sorted by (score descending, row ascending) into boxes_s / scores_s / labels_s /
+ *   src_s [B, N] (N = T K) for mq_ml_nms; nvalid / ndrop [B] (zeroed by the caller) = rows kept / rows dropped by the class filter.
+ * mq_tta_merge_finalize: keep [B, N] of mq_ml_nms -> the top_n cut (kthvalue, ties kept) and the rows ordered by (class-list position, row) in
+ *   boxes_o [B, N, 4], scores_o [B, N] fp32, labels_o [B, N] int64; counts [B] (zeroed by the caller) = live rows; thr [B] fp32 work.
+ * Replaces box_aug.py:21-63 (un-flip via BoxList.transpose, remove_boxes, BoxList.resize, cat) and :150-238
+ *   (merge_result_from_multi_scales + boxlist_nms with SPECIAL_NMS 'none' = _C.nms per class, csrc/cuda/nms.cu). */
+int mq_tta_merge_prep(const float* packed, const int* counts, const float* tparam, const float* band, const int* cls_rank,
+                      int n_cls, float* boxes, float* scores, int* labels, unsigned char* valid, float* boxes_s, float* scores_s,
+                      int* labels_s, int* src_s, int* nvalid, int* ndrop, int T, int B, int K, void* stream);
+int mq_tta_merge_finalize(const float* boxes_s, const float* scores_s, const int* labels_s, const int* src_s, const unsigned char* keep,
+                          const int* nvalid, float* thr, const int* cls_rank, float* boxes_o, float* scores_o, long long* labels_o, int* counts, int B, int N,
+                          int top_n, void* stream);
+
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --
  *     packed[((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8] = W[n][k]

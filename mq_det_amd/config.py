@@ -132,11 +132,16 @@ def get_cfg():
         AUGMENT_IMAGE_WITH_QUERY=False, RETURN_ATTN_GATE_VALUE=False, EXPAND_RATIO=1.5, MAX_QUERY_NUMBER=5000,
         SIMILARITY_THRESHOLD=0.85))
     cfg.TEST = C(dict(IMS_PER_BATCH=8, CHUNKED_EVALUATION=-1, MDETR_STYLE_AGGREGATE_CLASS_NUM=-1,
-                      USE_MULTISCALE=False, EVAL_TASK="detection"))
+                      USE_MULTISCALE=False, EVAL_TASK="detection",
+                      # test-time augmentation, read by mq_det_amd.tta.im_detect_bbox_aug (defaults.py:855-866)
+                      SCALES=(400, 500, 600, 640, 700, 900, 1000, 1100, 1200, 1300, 1400, 1800),
+                      RANGES=((96, 10000), (96, 10000), (64, 10000), (64, 10000), (64, 10000), (0, 10000), (0, 10000), (0, 256),
+                              (0, 256), (0, 192), (0, 192), (0, 96)),
+                      MAX_SIZE=2500, FLIP=True, SPECIAL_NMS="none", TH=0.6, PRE_NMS_TOP_N=1000, NUM_CLASSES=81, SELECT_CLASSES=()))
     cfg.DATALOADER = C(dict(SIZE_DIVISIBILITY=32, NUM_WORKERS=0))
     cfg.DATASETS = C(dict(SEPARATION_TOKENS=". ", ONE_HOT=False))
     cfg.INPUT = C(dict(PIXEL_MEAN=[103.530, 116.280, 123.675], PIXEL_STD=[57.375, 57.120, 58.395],
-                       MIN_SIZE_TEST=800, MAX_SIZE_TEST=1333))
+                       MIN_SIZE_TEST=800, MAX_SIZE_TEST=1333, TO_BGR255=True, FORMAT=""))                 # :68-77
     cfg.GLIPKNOW = C(dict(KNOWLEDGE_FILE="", PARALLEL_LANGUAGE_INPUT=False))
     # config/defaults.py:944-1001 (key names are the reference's: the flag system is part of the boundary)
     cfg.GROUNDINGDINO = C(dict(

@@ -67,6 +67,9 @@ _SIGNATURES = {
     "mq_ml_nms_workspace_bytes": (_l, [_i, _i]),
     "mq_ml_nms_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
     "mq_ml_nms": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "mq_tta_ingest_fwd": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp, _i, _i, _vp]),
+    "mq_tta_merge_prep": (_i, [_vp] * 5 + [_i] + [_vp] * 10 + [_i, _i, _i, _vp]),
+    "mq_tta_merge_finalize": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
@@ -1502,3 +1505,51 @@ def ml_nms(boxes, labels, nvalid, thresh, max_keep=0, as_bool=True):
     _chk(lib.mq_ml_nms(_ptr(boxes), _ptr(labels), _ptr(nvalid), _ptr(ws), _ptr(keep), B, N, float(thresh), _stream()),
          "mq_ml_nms")
     return keep.bool() if as_bool else keep
+
+
+# ---- test-time augmentation (csrc/tta.hip; host side: mq_det_amd/tta.py)
+TTA_MERGE_MAX_ROWS = 256 * 64                 # rows per image the merge's NMS (mq_ml_nms, the full sweep) takes
+def tta_ingest(src, src_off, meta, bounds, coef, B, Hp, Wp, TH, R, mean, std, bgr, x255, flip, err):
+    """Packed uint8 HWC images -> (canvas [B, 3, Hp, Wp] fp32, flipped canvas or None); tables from mq_det_amd.tta.ingest_tables.
+    err: int32 [1] on the device, set when a tile's input rows exceed R (the caller checks it once per batch)."""
+    lib = load_library()
+    _need_gpu(src, src_off, meta, bounds, coef, err)
+    assert src.dtype == torch.uint8 and src_off.dtype == torch.int64 and meta.dtype == bounds.dtype == coef.dtype == torch.int32
+    out = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=src.device)
+    out_f = torch.empty_like(out) if flip else None
+    m, s = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    with _timed("tta_ingest", src.numel() + out.numel() * 4 * (2 if flip else 1)):
+        _chk(lib.mq_tta_ingest_fwd(_ptr(src), _ptr(src_off), _ptr(meta), _ptr(bounds), _ptr(coef), _ptr(out), _ptr(out_f), _ptr(err), B, Hp, Wp, TH, R,
+                                   ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), int(bgr), int(x255), _stream()),
+             "mq_tta_ingest_fwd")
+    return out, out_f
+
+
+def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n):
+    """packed [T, B, K, 6] fp32, counts [T, B] int32, tparam [T, B, 4] fp32, band [T, 2] fp32 or None, cls_rank [L] int32 (-1 = dropped) ->
+    (boxes [B, N, 4], scores [B, N], labels [B, N] int64, counts [B] int32, dropped-by-class [B] int32); rows past counts[b] are junk."""
+    lib = load_library()
+    _need_gpu(packed, counts, tparam, band, cls_rank)
+    T, B, K, _ = packed.shape
+    N, dev = T * K, packed.device
+    assert packed.dtype == torch.float32 and packed.is_contiguous() and counts.dtype == torch.int32 and cls_rank.dtype == torch.int32
+    f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)          # noqa: E731
+    i = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)            # noqa: E731
+    boxes, scores, labels, valid = f(B, N, 4), f(B, N), i(B, N), torch.empty(B, N, dtype=torch.uint8, device=dev)
+    boxes_s, scores_s, labels_s, src_s = f(B, N, 4), f(B, N), i(B, N), i(B, N)
+    nz = torch.zeros(3, B, dtype=torch.int32, device=dev)
+    nvalid, ndrop, n_out = nz[0], nz[1], nz[2]
+    _chk(lib.mq_tta_merge_prep(_ptr(packed), _ptr(counts), _ptr(tparam), _ptr(band), _ptr(cls_rank), cls_rank.numel(), _ptr(boxes), _ptr(scores),
+                               _ptr(labels), _ptr(valid), _ptr(boxes_s), _ptr(scores_s), _ptr(labels_s), _ptr(src_s), _ptr(nvalid),
+                               _ptr(ndrop), T, B, K, _stream()), "mq_tta_merge_prep")
+    if thresh > 0:                             # boxlist_nms: thresh <= 0 returns the rows as they are
+        if N > TTA_MERGE_MAX_ROWS:
+            raise ValueError(f"TTA merge: {N} rows per image (transforms x detection slots) exceed the {TTA_MERGE_MAX_ROWS} of mq_ml_nms")
+        keep = ml_nms(boxes_s, labels_s, nvalid, thresh, as_bool=False)           # max_keep 0: the full sweep, never the early stop
+    else:
+        keep = torch.ones(B, N, dtype=torch.uint8, device=dev)
+    boxes_o, scores_o, labels_o, thr = f(B, N, 4), f(B, N), torch.empty(B, N, dtype=torch.int64, device=dev), f(B)
+    _chk(lib.mq_tta_merge_finalize(_ptr(boxes_s), _ptr(scores_s), _ptr(labels_s), _ptr(src_s), _ptr(keep), _ptr(nvalid), _ptr(thr),
+                                   _ptr(cls_rank), _ptr(boxes_o), _ptr(scores_o), _ptr(labels_o), _ptr(n_out), B, N, int(top_n), _stream()),
+         "mq_tta_merge_finalize")
+    return boxes_o, scores_o, labels_o, n_out, ndrop

@@ -8,6 +8,9 @@ import math
 
 import torch
 
+FLIP_LEFT_RIGHT = 0
+FLIP_TOP_BOTTOM = 1
+
 
 class BoxList:
     def __init__(self, bbox, image_size, mode="xyxy"):
@@ -55,6 +58,21 @@ class BoxList:
         out = BoxList(b, size, "xyxy")
         for k, v in self.extra_fields.items():
             out.add_field(k, v.resize(size) if hasattr(v, "resize") and not torch.is_tensor(v) else v)
+        return out.convert(self.mode)
+
+    def transpose(self, method):
+        """bounding_box.py:141-177: FLIP_LEFT_RIGHT (0) / FLIP_TOP_BOTTOM (1) in the image frame, legacy TO_REMOVE = 1 for left-right."""
+        if method not in (FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM):
+            raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
+        w, h = self.size
+        x1, y1, x2, y2 = self.convert("xyxy").bbox.split(1, dim=-1)
+        if method == FLIP_LEFT_RIGHT:
+            box = torch.cat([w - x2 - 1, y1, w - x1 - 1, y2], -1)
+        else:
+            box = torch.cat([x1, h - y2, x2, h - y1], -1)
+        out = BoxList(box, self.size, "xyxy")
+        for k, v in self.extra_fields.items():
+            out.add_field(k, v.transpose(method) if hasattr(v, "transpose") and not torch.is_tensor(v) else v)
         return out.convert(self.mode)
 
     def clip_to_image(self, remove_empty=True):
