@@ -13,7 +13,9 @@ EVERY step computes the whole forward: the per-image feature cache and the per-c
  are switched OFF for this workload -- the synthetic loop re-sends the same tensors, and skipping the
 backbone would be work skipped inside the timed region.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields.  A plain run does nothing else: set up, warm up, time the steps, write
+--dump-outputs if asked, print the line.  With --full it also measures, after the timed steps, and reports (the full record
+in bench_extras.json)
   roofline       the hand-written kernel that takes the most time per step (timed live with HIP events on the launch stream)
   rooflines      the same record for every hot hand-written kernel: MFMA-bound (TFLOP/s vs 2.5 PFLOP/s dense fp16) with the
                  ALGORITHMIC and the EXECUTED flop counts side by side, HBM-bound (algorithmic GB/s vs 8 TB/s)
@@ -26,6 +28,8 @@ Rank 0 prints ONE JSON line with the contract fields plus
   cpu_baseline   (N = 1) BASELINE.md section 3 / configs[0]: the fp32 CPU oracle, GLIP-T without vision queries, one 800x1333
                  image, 20-token caption, 2 warm-up + 5 timed forwards, median.
 
+    --full            the records above, each from an eager pass or a bounded subprocess of its own; without it the run's
+                      time is set-up + warm-up + the timed steps.
     --workload lvis   BASELINE.json configs[2] shape on this many GPUs: 1203 synthetic categories -> 31 chunk captions of
                       <= 40 classes, each step = a NEW batch of images x 31 forwards (the LVIS protocol of
                       engine/inference.py:605-625) with the boundary's caches ON; value = forwards/s, plus LVIS-style
@@ -232,8 +236,8 @@ def main_gdino(args, rank, world, dev):
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
-    kern, prof_steps = {}, 0
-    if rank == 0:
+    kern, stages, prof_steps = {}, {}, 0
+    if rank == 0 and args.full:
         prof_steps = min(2, args.steps)
         ops.start_timing()
         for _ in range(prof_steps):
@@ -246,6 +250,7 @@ def main_gdino(args, rank, world, dev):
             model(images, captions=captions, positive_map=pmap)
         stages = gp.stop_marks()
         model.use_hip_graph = graph_on
+    if rank == 0:
         ips = world * Bn * args.steps / dt
         res = {"metric": "images/sec MQ-GroundingDINO-T 800×1333 5-shot vision queries", "value": round(ips, 3), "unit": "images/sec",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
@@ -257,12 +262,13 @@ def main_gdino(args, rank, world, dev):
                           "box_threshold": f"{bench_thr:.4f} = median query score of a probe forward (the yaml's {yaml_thr} leaves no survivor with random weights)"},
                "detections_img0": len(out[0]), "hip_graph": bool(model.use_hip_graph and any(e.get("stage") == 2 for e in model._graphs.values())),
                "cache_stats": dict(model.cache_stats), "model_tflops": round(ips * GFLOP_PER_IMAGE_GDINO / 1e3, 2),
-               "model_frac_of_mfma_peak": round(ips * GFLOP_PER_IMAGE_GDINO / 1e3 / (MFMA_PEAK_TFLOPS * world), 4),
-               "kernels_ms_per_step": {k: round(v[1] / max(prof_steps, 1), 3) for k, v in sorted(kern.items())},
-               "kernels_gbs": {k: round(v[2] / (v[1] * 1e-3) / 1e9, 1) for k, v in sorted(kern.items()) if v[2] and v[1] > 0},
-               "stages_ms_per_step": {k: round(v / max(prof_steps, 1), 3) for k, v in stages.items()},
-               "timing": "kernels_ms_per_step: HIP events around each hand-written launch in an eager pass of the same step; "
-                         "stages_ms_per_step: HIP events between pipeline stages in an eager pass (host launch gaps included)"}
+               "model_frac_of_mfma_peak": round(ips * GFLOP_PER_IMAGE_GDINO / 1e3 / (MFMA_PEAK_TFLOPS * world), 4)}
+        if args.full:
+            res.update({"kernels_ms_per_step": {k: round(v[1] / max(prof_steps, 1), 3) for k, v in sorted(kern.items())},
+                        "kernels_gbs": {k: round(v[2] / (v[1] * 1e-3) / 1e9, 1) for k, v in sorted(kern.items()) if v[2] and v[1] > 0},
+                        "stages_ms_per_step": {k: round(v / max(prof_steps, 1), 3) for k, v in stages.items()},
+                        "timing": "kernels_ms_per_step: HIP events around each hand-written launch in an eager pass of the same step; "
+                                  "stages_ms_per_step: HIP events between pipeline stages in an eager pass (host launch gaps included)"})
         msda = [(k, v) for k, v in kern.items() if k.startswith("msdeform_attn_q")]
         if msda:                                   # the gather kernel of the deformable attention: bound by 64-byte corner rows through L2
             k, v = max(msda, key=lambda kv: kv[1][1])
@@ -273,11 +279,11 @@ def main_gdino(args, rank, world, dev):
                                "avg_launch_ms": round(v[1] / v[0], 4), "l2_gather_GBs": round(gathered / (v[1] * 1e-3) / 1e9, 1),
                                "note": "achieved = ALGORITHMIC bytes (value once + projection + output) / time; l2_gather_GBs = bytes of the 64-byte "
                                        "corner rows the gather pulls through L2 -> L1 (the real bound, DESIGN.md 11)"}
-        if world == 1 and args.cpu_baseline:
+        if world == 1 and args.full and args.cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(timeout=300, flag="--cpu-baseline-worker-gdino")
         if dumped is not None:
             res["dumped_outputs"] = dump_outputs(dumped, args.dump_outputs)
-        print(compact_line(res, args.extras_file or os.path.join(ROOT, "bench_extras_gdino.json"), write=bool(args.extras_file) or not args.no_extras), flush=True)
+        print(compact_line(res, args.extras_file or os.path.join(ROOT, "bench_extras_gdino.json"), write=bool(args.extras_file) or (args.full and not args.no_extras)), flush=True)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -659,10 +665,10 @@ def lang_path_b64(model, cfg, dev, chunks, iters=5):
 
 def _sub_bench(argv, env=None, timeout=150, keep=()):
     """One more invocation of this script in a subprocess with a hard time limit (so that nothing it does can cost the headline line);
-    returns a summary of the JSON line it printed."""
+    returns a summary of the JSON line it printed.  --full --no-extras: the sub-run's line keeps its roofline record."""
     import subprocess
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), *argv, "--no-extras"], env=dict(os.environ, **(env or {})),
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), *argv, "--full", "--no-extras"], env=dict(os.environ, **(env or {})),
                            capture_output=True, text=True, timeout=timeout)
         for line in reversed(r.stdout.strip().splitlines()):
             if line.startswith("{"):
@@ -759,8 +765,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lang-b64", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline line's timed steps, also measure what it does not need: per-kernel "
+                                                        "rooflines, lang_path_b64, the split-precise and other BASELINE configs (subprocesses), "
+                                                        "the CPU baseline; writes bench_extras.json")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-lang-b64", action="store_true", help="with --full: skip lang_path_b64")
     ap.add_argument("--batch", type=int, default=B_PER_GPU)
     ap.add_argument("--workload", choices=["mq-glip-t", "lvis", "mq-glip-l", "mq-gdino-t"], default="mq-glip-t")
     ap.add_argument("--caption", choices=["lvis", "short"], default="lvis", help="lvis: 1-4 word class names, 141 tokens (default); "
@@ -772,11 +781,11 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay (for PMC profiling)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-worker-gdino", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-experimental", action="store_true", help="skip the kernel-set A/B and the other BASELINE configs (subprocesses)")
+    ap.add_argument("--no-experimental", action="store_true", help="with --full: skip the split-precise and the other BASELINE configs (subprocesses)")
     ap.add_argument("--extras-file", default=None, help="write the full record (rooflines, kernels_ms_per_step, sub-runs ...) to this path; default: "
-                                                         "bench_extras.json next to this script, nothing under --no-extras")
-    ap.add_argument("--no-extras", action="store_true", help="the contract fields + rooflines only (what the subprocess lines use)")
-    ap.add_argument("--cpu-baseline", action="store_true", help="mq-gdino-t workload: also time the CPU oracle (off by default there)")
+                                                         "bench_extras.json next to this script with --full, nothing without it or under --no-extras")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the contract fields + rooflines only (what the subprocess lines use)")
+    ap.add_argument("--cpu-baseline", action="store_true", help="with --full and the mq-gdino-t workload: also time the CPU oracle (off by default there)")
     ap.add_argument("--overlap-gather", action="store_true", help="N > 1: the gather of step k runs asynchronously under the forward of step k + 1 "
                                                                   "(parallel.OverlappedGather); the last one is waited for inside the timed region")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
@@ -889,7 +898,7 @@ def main():
     # per-kernel durations: HIP events around the launches (same kernels, same inputs) in a short EAGER pass --
     # inside a graph replay individual launches cannot be bracketed by events
     kern, prof_steps = {}, 0
-    if rank == 0 and not lvis:
+    if rank == 0 and not lvis and args.full:
         prof_steps = min(3, args.steps)
         # single-stream for this pass: with the level / text streams active, concurrent kernels share the CUs and an
         # event-bracketed duration would include its neighbours (the timed region above keeps the multi-stream schedule)
@@ -948,42 +957,43 @@ def main():
                                   "reference_algorithmic_tflops": round(ips * gf / 1e3, 2),
                                   "note": "model_tflops = EXECUTED flops (bench.executed_gflop_per_image: projections folded, K / V per unique vision "
                                           "token, live text blocks only) x images/s; the reference's un-folded count at T = 256 beside it"}
-            res["roofline"] = roof
-            res["rooflines"] = roofs
-            res["kernels_ms_per_step"] = {k: round(v[1] / max(prof_steps, 1), 3) for k, v in sorted(kern.items())}
             res["kernel_selection"] = dict(ops.KERNELS)
-            res["pmc_traffic_file"] = _pmc().get("_file")
-            res["timing"] = "roofline records: HIP events on the launch stream around each launch, eager single-stream pass of the same steps"
-            want_cpu = world == 1 and not args.no_cpu_baseline and not large
-            if world == 1 and not args.no_lang_b64 and not large:
-                try:
-                    res["lang_path_b64"] = lang_path_b64(model, cfg, dev, chunks)
-                except Exception as e:  # noqa: BLE001
-                    res["lang_path_b64"] = {"error": repr(e)[:300]}
-            if world == 1 and not args.no_experimental and not large and args.dtype == "f16" and not any(k in os.environ for k in tuple(ROUND3_KERNEL_SET) + tuple(ROUND4_KERNEL_SET) if k.startswith("MQ_")):
-                # bounded subprocess lines, most informative first; each only while the whole run stays within a few minutes
-                if time.perf_counter() - t_start < 200:
-                    # the SPLIT-PRECISE mode (MODEL.COMPUTE_DTYPE = float32: fp32 operands carried as hi + lo through three fp16 MFMAs -- what the 1e-3
-                    # parity tests run) on the SAME workload at the SAME batch: its images/s beside the fp16 line
-                    res["split_precise"] = _sub_bench(["--dtype", "f32", "--batch", str(Bn), "--steps", "5", "--warmup", "2"], None, 150)
-                    res["split_precise"].pop("workload", None)
-                other = {}
-                for key, argv, limit in (("configs[3] mq-glip-l bf16 B=4", ["--workload", "mq-glip-l", "--dtype", "bf16", "--steps", "5", "--warmup", "2"], 160),
-                                         ("configs[4] mq-gdino-t B=16", ["--workload", "mq-gdino-t", "--steps", "5", "--warmup", "2"], 200),
-                                         ("configs[2] lvis B=8 chunk-batch 32", ["--workload", "lvis", "--chunk-batch", "32", "--steps", "2", "--warmup", "2"], 240)):
-                    if time.perf_counter() - t_start < limit:
-                        other[key] = _sub_bench(argv, None, 150, keep=("roofline", "model_tflops", "lvis_style_images_per_sec", "forwards_per_step"))
-                res["other_configs"] = other
-            if want_cpu:
-                # AFTER the GPU sub-runs, not beside them: GPU call 4 of round 6 ran the worker concurrently -- its median went from 5.7 to 12.2 s per
-                # forward and the sub-runs lost 10 - 45 % (host threads of the replayed graphs compete with 32 pinned OpenMP threads)
-                try:
-                    res["cpu_baseline"] = cpu_baseline()
-                except Exception as e:  # noqa: BLE001
-                    res["cpu_baseline"] = {"error": repr(e)[:200]}
+            if args.full:
+                res["roofline"] = roof
+                res["rooflines"] = roofs
+                res["kernels_ms_per_step"] = {k: round(v[1] / max(prof_steps, 1), 3) for k, v in sorted(kern.items())}
+                res["pmc_traffic_file"] = _pmc().get("_file")
+                res["timing"] = "roofline records: HIP events on the launch stream around each launch, eager single-stream pass of the same steps"
+                want_cpu = world == 1 and not args.no_cpu_baseline and not large
+                if world == 1 and not args.no_lang_b64 and not large:
+                    try:
+                        res["lang_path_b64"] = lang_path_b64(model, cfg, dev, chunks)
+                    except Exception as e:  # noqa: BLE001
+                        res["lang_path_b64"] = {"error": repr(e)[:300]}
+                if world == 1 and not args.no_experimental and not large and args.dtype == "f16" and not any(k in os.environ for k in tuple(ROUND3_KERNEL_SET) + tuple(ROUND4_KERNEL_SET) if k.startswith("MQ_")):
+                    # bounded subprocess lines, most informative first; each only while the whole run stays within a few minutes
+                    if time.perf_counter() - t_start < 200:
+                        # the SPLIT-PRECISE mode (MODEL.COMPUTE_DTYPE = float32: fp32 operands carried as hi + lo through three fp16 MFMAs -- what the 1e-3
+                        # parity tests run) on the SAME workload at the SAME batch: its images/s beside the fp16 line
+                        res["split_precise"] = _sub_bench(["--dtype", "f32", "--batch", str(Bn), "--steps", "5", "--warmup", "2"], None, 150)
+                        res["split_precise"].pop("workload", None)
+                    other = {}
+                    for key, argv, limit in (("configs[3] mq-glip-l bf16 B=4", ["--workload", "mq-glip-l", "--dtype", "bf16", "--steps", "5", "--warmup", "2"], 160),
+                                             ("configs[4] mq-gdino-t B=16", ["--workload", "mq-gdino-t", "--steps", "5", "--warmup", "2"], 200),
+                                             ("configs[2] lvis B=8 chunk-batch 32", ["--workload", "lvis", "--chunk-batch", "32", "--steps", "2", "--warmup", "2"], 240)):
+                        if time.perf_counter() - t_start < limit:
+                            other[key] = _sub_bench(argv, None, 150, keep=("roofline", "model_tflops", "lvis_style_images_per_sec", "forwards_per_step"))
+                    res["other_configs"] = other
+                if want_cpu:
+                    # AFTER the GPU sub-runs, not beside them: with the worker running concurrently (round 6) its median went from 5.7 to 12.2 s per
+                    # forward and the sub-runs lost 10 - 45 % (host threads of the replayed graphs compete with 32 pinned OpenMP threads)
+                    try:
+                        res["cpu_baseline"] = cpu_baseline()
+                    except Exception as e:  # noqa: BLE001
+                        res["cpu_baseline"] = {"error": repr(e)[:200]}
         if dumped is not None:
             res["dumped_outputs"] = dump_outputs(dumped, args.dump_outputs)
-        print(compact_line(res, args.extras_file, write=bool(args.extras_file) or not args.no_extras), flush=True)
+        print(compact_line(res, args.extras_file, write=bool(args.extras_file) or (args.full and not args.no_extras)), flush=True)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
