@@ -470,6 +470,23 @@ int mq_tta_merge_finalize(const float* boxes_s, const float* scores_s, const int
                           const int* nvalid, float* thr, const int* cls_rank, float* boxes_o, float* scores_o, long long* labels_o, int* counts, int B, int N,
                           int top_n, void* stream);
 
+/* ---- LVIS Fixed AP (csrc/lvis_eval.hip, host side mq_det_amd/evaluation.py LvisFixedAPEvaluator).  fp64 / fp32 / integer data only.
+ * mq_lvis_match: LVISEval.evaluate_img for P (image, category) pairs.  pair_dt / pair_gt [P, 2] int32 = (first, count) of the pair's detections
+ *   (sorted by score, dt_box [*, 4] fp32 xywh) and ground truths (annotation-file order: gt_box [*, 4] fp64 xywh, gt_area fp64, gt_ign uint8 =
+ *   `ignore`, gt_nz uint8 = id != 0); pair_nel [P] uint8 = category in the image's not_exhaustive_category_ids; area_rng [4, 2] and iou_thr [10]
+ *   fp64 (the reference's tables).  -> dt_bits [*, 2] uint64 per detection: bit area * 10 + threshold of word 0 = matched to a ground truth of
+ *   non-zero id, of word 1 = ignored; gt_count [P, 4] int32 = non-ignored ground truths per area range.  ws: uint8 [40, Ng] (Ng = ground truths in
+ *   all), the taken flags of pairs with more than 512 ground truths.
+ * mq_lvis_accumulate: LVISEval.accumulate for K categories: the detections of category k are dt_bits rows order[cat_off[k] .. cat_off[k + 1])
+ *   in the reference's order (score descending, image id, position in the pair); num_gt [K, 4] int32; rec_thr [101] fp64 ->
+ *   precision [10, 101, K, 4] and recall [10, K, 4] fp64 (-1 where num_gt == 0).
+ * Replaces lvis_eval.py:252-523 (LVISEval.evaluate / compute_iou with pycocotools' bbIou / evaluate_img / accumulate) with max_dets = -1. */
+int mq_lvis_match(const int* pair_dt, const int* pair_gt, const unsigned char* pair_nel, const float* dt_box, const double* gt_box,
+                  const double* gt_area, const unsigned char* gt_ign, const unsigned char* gt_nz, const double* area_rng, const double* iou_thr,
+                  unsigned long long* dt_bits, int* gt_count, unsigned char* ws, int P, long Ng, void* stream);
+int mq_lvis_accumulate(const int* cat_off, const int* order, const unsigned long long* dt_bits, const int* num_gt, const double* rec_thr,
+                       double* precision, double* recall, int K, void* stream);
+
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --
  *     packed[((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8] = W[n][k]

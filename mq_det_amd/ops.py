@@ -70,6 +70,8 @@ _SIGNATURES = {
     "mq_tta_ingest_fwd": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp, _i, _i, _vp]),
     "mq_tta_merge_prep": (_i, [_vp] * 5 + [_i] + [_vp] * 10 + [_i, _i, _i, _vp]),
     "mq_tta_merge_finalize": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
+    "mq_lvis_match": (_i, [_vp] * 13 + [_i, _l, _vp]),
+    "mq_lvis_accumulate": (_i, [_vp] * 7 + [_i, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
@@ -1553,3 +1555,42 @@ def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n):
                                    _ptr(cls_rank), _ptr(boxes_o), _ptr(scores_o), _ptr(labels_o), _ptr(n_out), B, N, int(top_n), _stream()),
          "mq_tta_merge_finalize")
     return boxes_o, scores_o, labels_o, n_out, ndrop
+
+
+# ---- LVIS Fixed AP (csrc/lvis_eval.hip; host side: mq_det_amd/evaluation.py LvisFixedAPEvaluator)
+LVIS_MATCH_LANES = 40                         # (area range, IoU threshold) scans per pair: the rows of the slow path's workspace
+
+
+def lvis_match(pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz, area_rng, iou_thr):
+    """evaluate_img for every pair -> (dt_bits [Nd, 2] int64 (uint64 bit patterns: matched, ignored; bit = area * 10 + threshold),
+    gt_count [P, 4] int32 non-ignored ground truths per area range).  Layouts: include/mqdet_hip.h mq_lvis_match."""
+    lib = load_library()
+    _need_gpu(pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz, area_rng, iou_thr)
+    assert pair_dt.dtype == pair_gt.dtype == torch.int32 and pair_nel.dtype == gt_ign.dtype == gt_nz.dtype == torch.uint8
+    assert dt_box.dtype == torch.float32 and gt_box.dtype == gt_area.dtype == area_rng.dtype == iou_thr.dtype == torch.float64
+    assert area_rng.numel() == 8 and iou_thr.numel() == 10
+    for t in (pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz):
+        assert t.is_contiguous()
+    P, Nd, Ng, dev = len(pair_dt), len(dt_box), len(gt_box), dt_box.device
+    dt_bits = torch.zeros(Nd, 2, dtype=torch.int64, device=dev)
+    gt_count = torch.zeros(P, 4, dtype=torch.int32, device=dev)
+    ws = torch.empty(LVIS_MATCH_LANES * max(Ng, 1), dtype=torch.uint8, device=dev)
+    with _timed("lvis_match"):
+        _chk(lib.mq_lvis_match(_ptr(pair_dt), _ptr(pair_gt), _ptr(pair_nel), _ptr(dt_box), _ptr(gt_box), _ptr(gt_area), _ptr(gt_ign), _ptr(gt_nz),
+                               _ptr(area_rng), _ptr(iou_thr), _ptr(dt_bits), _ptr(gt_count), _ptr(ws), P, Ng, _stream()), "mq_lvis_match")
+    return dt_bits, gt_count
+
+
+def lvis_accumulate(cat_off, order, dt_bits, num_gt, rec_thr, n_thr=10):
+    """accumulate -> (precision [10, 101, K, 4], recall [10, K, 4]) fp64.  Layouts: include/mqdet_hip.h mq_lvis_accumulate."""
+    lib = load_library()
+    _need_gpu(cat_off, order, dt_bits, num_gt, rec_thr)
+    assert cat_off.dtype == order.dtype == num_gt.dtype == torch.int32 and dt_bits.dtype == torch.int64 and rec_thr.dtype == torch.float64
+    assert rec_thr.numel() == 101 and n_thr == 10 and num_gt.is_contiguous() and dt_bits.is_contiguous()
+    K, dev = len(cat_off) - 1, dt_bits.device
+    precision = torch.empty(n_thr, 101, K, 4, dtype=torch.float64, device=dev)
+    recall = torch.empty(n_thr, K, 4, dtype=torch.float64, device=dev)
+    with _timed("lvis_accumulate"):
+        _chk(lib.mq_lvis_accumulate(_ptr(cat_off), _ptr(order), _ptr(dt_bits), _ptr(num_gt), _ptr(rec_thr), _ptr(precision), _ptr(recall), K,
+                                    _stream()), "mq_lvis_accumulate")
+    return precision, recall

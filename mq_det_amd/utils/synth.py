@@ -47,3 +47,55 @@ def randomize_(model, seed=0):
 def synthetic_bank(labels, channels=256, k=5, seed=1):
     g = torch.Generator().manual_seed(seed)
     return {int(l): torch.randn(k, 1, channels, generator=g) for l in labels}
+
+
+# LVIS v1 frequency split of its 1203 categories (rare / common / frequent)
+LVIS_FREQ_SPLIT = (337, 461, 405)
+
+
+def synthetic_lvis(n_img=4809, n_cat=1203, n_gt=50000, det_per_cat=10000, seed=0, neg_per_img=15, nel_per_img=2, hit_frac=0.3):
+    """Seeded LVIS-shaped ground truth (a dict in LVIS json format) and detections (numpy: image id, category id, score, x, y, w, h as
+    float32 rows, per category `det_per_cat` rows).  A `hit_frac` share of each category's detections are jittered copies of its ground
+    truths, the rest lie on random images (most of them fall outside the image's positive / negative categories, as in LVIS).  Scores
+    are quantised to 1/4096 so that ties occur."""
+    import numpy as np
+    g = np.random.default_rng(seed)
+    img_ids = np.sort(g.choice(np.arange(1, 600000), n_img, replace=False))
+    cat_ids = np.arange(1, n_cat + 1)
+    split = np.cumsum([round(n_cat * f / sum(LVIS_FREQ_SPLIT)) for f in LVIS_FREQ_SPLIT])
+    freq = ["r" if c < split[0] else "c" if c < split[1] else "f" for c in range(n_cat)]
+    wh = g.integers(320, 641, (n_img, 2))
+    gi = g.integers(0, n_img, n_gt)
+    gc = g.integers(0, n_cat, n_gt)
+    gw = np.maximum(g.random(n_gt) ** 2 * wh[gi, 0] * 0.8, 1.0)
+    gh = np.maximum(g.random(n_gt) ** 2 * wh[gi, 1] * 0.8, 1.0)
+    gx, gy = g.random(n_gt) * (wh[gi, 0] - gw), g.random(n_gt) * (wh[gi, 1] - gh)
+    anns = [{"id": int(n + 1), "image_id": int(img_ids[gi[n]]), "category_id": int(cat_ids[gc[n]]),
+             "bbox": [float(gx[n]), float(gy[n]), float(gw[n]), float(gh[n])], "area": float(gw[n] * gh[n])} for n in range(n_gt)]
+    images = []
+    for i in range(n_img):
+        neg = g.choice(n_cat, neg_per_img, replace=False)
+        nel = g.choice(n_cat, nel_per_img, replace=False)
+        images.append({"id": int(img_ids[i]), "width": int(wh[i, 0]), "height": int(wh[i, 1]),
+                       "neg_category_ids": [int(cat_ids[c]) for c in neg], "not_exhaustive_category_ids": [int(cat_ids[c]) for c in nel]})
+    gt = {"images": images, "annotations": anns,
+          "categories": [{"id": int(c), "name": f"c{c}", "frequency": f} for c, f in zip(cat_ids, freq)]}
+    by_cat = [[] for _ in range(n_cat)]
+    for n in range(n_gt):
+        by_cat[gc[n]].append(n)
+    rows = np.zeros((n_cat * det_per_cat, 7), np.float32)
+    for c in range(n_cat):
+        r = rows[c * det_per_cat:(c + 1) * det_per_cat]
+        nh = int(det_per_cat * hit_frac) if by_cat[c] else 0
+        src = np.asarray(by_cat[c], np.int64)[g.integers(0, max(len(by_cat[c]), 1), nh)] if nh else np.zeros(0, np.int64)
+        ri = g.integers(0, n_img, det_per_cat - nh)
+        r[:, 1] = cat_ids[c]
+        r[:nh, 0] = img_ids[gi[src]]
+        r[nh:, 0] = img_ids[ri]
+        j = lambda v, s: v * (1 + s * g.standard_normal(len(v)))                          # noqa: E731
+        r[:nh, 3], r[:nh, 4] = j(gx[src] + 1, 0.05), j(gy[src] + 1, 0.05)
+        r[:nh, 5], r[:nh, 6] = j(gw[src], 0.1), j(gh[src], 0.1)
+        rw, rh = g.random(len(ri)) * wh[ri, 0] * 0.5 + 1, g.random(len(ri)) * wh[ri, 1] * 0.5 + 1
+        r[nh:, 3], r[nh:, 4], r[nh:, 5], r[nh:, 6] = g.random(len(ri)) * (wh[ri, 0] - rw), g.random(len(ri)) * (wh[ri, 1] - rh), rw, rh
+        r[:, 2] = np.floor(g.random(det_per_cat) * 4096) / 4096
+    return gt, rows
