@@ -487,6 +487,17 @@ int mq_lvis_match(const int* pair_dt, const int* pair_gt, const unsigned char* p
 int mq_lvis_accumulate(const int* cat_off, const int* order, const unsigned long long* dt_bits, const int* num_gt, const double* rec_thr,
                        double* precision, double* recall, int K, void* stream);
 
+/* ---- Vision-query bank (csrc/query_bank.hip, host side mq_det_amd/query_bank.py QueryBank).  fp32 / integer data only.
+ * The admission loop of generalized_vl_rcnn_new.py:269-287 (== groundingdino.py:401-421) for N candidates in one launch.  cand [N, D] fp32
+ * (D = scales x channels); sorted_labels / order [N] int64 = the candidates' labels after ONE stable sort and the sort's permutation; workgroup b
+ * walks the candidates of label label_lo + b (b < num_labels) in row order.  Bank: pool [pool_rows, D] fp32 append-only rows, inv_norm
+ * [pool_rows] fp32 = 1 / max(|row|, 1e-12), slots [labels, cap] int32 = pool rows of a label in admission order, counts [labels] int32;
+ * state [2] int32 = (pool rows in use, 1 if the pool overflowed -- the host sizes it for every candidate, so never).  A candidate is skipped
+ * when its label holds maxq (<= cap) rows, or -- exclude != 0, label not empty -- when a row of the label has cosine similarity > thr
+ * (strict; NaN compares false).  Admitted rows are copied bit for bit.  Every label label_lo .. label_lo + num_labels - 1 must be < labels. */
+int mq_bank_admit(const float* cand, const long long* sorted_labels, const long long* order, float* pool, float* inv_norm, int* slots, int* counts,
+                  int* state, int N, int D, int pool_rows, int cap, int label_lo, int num_labels, int maxq, int exclude, float thr, void* stream);
+
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --
  *     packed[((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8] = W[n][k]

@@ -130,7 +130,9 @@ def get_cfg():
         NO_CAT=True, FIX_ATTN_GATE=-1.0, ADD_ADAPT_LAYER=False, QUERY_FUSION=False, DISABLE_SELECTOR=False,
         LEARNABLE_BANK=False, ADD_VISION_LAYER=False, RANDOM_KSHOT=False, MASK_DURING_INFERENCE=False,
         AUGMENT_IMAGE_WITH_QUERY=False, RETURN_ATTN_GATE_VALUE=False, EXPAND_RATIO=1.5, MAX_QUERY_NUMBER=5000,
-        SIMILARITY_THRESHOLD=0.85))
+        SIMILARITY_THRESHOLD=0.85,
+        # the bank-building and test-time online-update loops (mq_det_amd.query_bank; defaults.py:903-935)
+        DATASET_NAME="", MAX_TEST_QUERY_NUMBER=100, SCORE_THRESHOLD=0.6, NUM_TURNS=1, QUERY_ADDITION_NAME="", QUERY_BANK_SAVE_PATH=""))
     cfg.TEST = C(dict(IMS_PER_BATCH=8, CHUNKED_EVALUATION=-1, MDETR_STYLE_AGGREGATE_CLASS_NUM=-1,
                       USE_MULTISCALE=False, EVAL_TASK="detection",
                       # test-time augmentation, read by mq_det_amd.tta.im_detect_bbox_aug (defaults.py:855-866)

@@ -1,0 +1,136 @@
+// The vision-query bank's admission loop on the device (host side: mq_det_amd/query_bank.py QueryBank.update).
+//
+// mq_bank_admit: generalized_vl_rcnn_new.py:269-287 (== groundingdino.py:401-421) for a whole batch of candidates in one launch.  The host
+// sorts the candidates' labels once (stable: candidates of a label keep their row order); workgroup b owns label `label_lo + b`, finds its
+// segment of the sorted labels by two binary searches and walks the candidates IN ORDER -- a candidate admitted earlier in the call is part
+// of the bank the later ones are compared against.  Labels are independent, so the sequential semantics of the reference hold exactly.
+//
+// Per candidate: stop when the label holds maxq rows; with `exclude` and a non-empty label bank the candidate is skipped when any row has
+// cosine similarity > thr (strict; a NaN compares false, so the candidate is admitted, like `(similarity > thr).sum() > 0`).  The cosine
+// is dot(c, r) / (max(|c|, 1e-12) max(|r|, 1e-12)) -- F.normalize's rule -- with 1 / max(|r|, 1e-12) of every bank row cached in inv_norm,
+// so a comparison is ONE dot product: the bank rows are dealt out over the four waves, the row is read with 16-byte loads (1 KB per wave
+// instruction at C = 256), the candidate sits in registers (C = 256) or comes from the cache, a per-lane partial dot and a wave reduction
+// follow.  The any-hit flag crosses the waves through LDS with one barrier per candidate (three flags in rotation: the flag of candidate
+// i + 1 is cleared while candidate i is decided, two barriers after its last reader).  An admitted row is copied bit for bit into a pool
+// row taken with one atomic add by one lane; slot, inverse norm and count are plain stores by one lane; two more barriers make the new
+// row visible to the next candidate's comparisons.
+//
+// What bounds it: the walk through one label's candidates is sequential, and each comparison pass reads the label's rows from L2 / HBM:
+// n rows x D floats over four waves.  One launch replaces, per candidate, the dict path's two normalisations, einsum, compare, reduction,
+// device->host sync and torch.cat of the label's whole tensor.
+#include "common.h"
+
+MQ_NAMESPACE_BEGIN
+#ifdef MQ_PRIMARY_UNIT                                     // fp32 / integer data only: one copy, in the fp16 translation unit
+
+#define BANK_WAVES 4
+#define BANK_THREADS (BANK_WAVES * 64)
+
+// first index in [0, n) whose value is >= v (n if none)
+__device__ __forceinline__ int bank_lower_bound(const long long* __restrict__ a, int n, long long v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+template <bool VEC4>
+__device__ __forceinline__ float bank_dot(const float* __restrict__ a, const float* __restrict__ b, int D, int lane) {
+  float s = 0.f;
+  if (VEC4) {
+    for (int k = lane * 4; k < D; k += 256) {
+      const float4_ x = *(const float4_*)(a + k), y = *(const float4_*)(b + k);
+      s += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
+    }
+  } else {
+    for (int k = lane; k < D; k += 64) s += a[k] * b[k];
+  }
+  return wave_sum(s);
+}
+
+template <bool VEC4>
+__global__ __launch_bounds__(BANK_THREADS) void bank_admit_kernel(const float* __restrict__ cand, const long long* __restrict__ sorted_labels,
+                                                                   const long long* __restrict__ order, float* pool, float* inv_norm,
+                                                                   int* slots, int* __restrict__ counts, int* __restrict__ state, int N, int D,
+                                                                   int pool_rows, int cap, int label_lo, int maxq, int exclude, float thr) {
+  __shared__ int hit_s[3];
+  __shared__ int prow_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long l = (long long)label_lo + blockIdx.x;
+  const int lo = bank_lower_bound(sorted_labels, N, l), hi = bank_lower_bound(sorted_labels, N, l + 1);
+  if (lo >= hi) return;                                    // no candidate of this label
+  int* __restrict__ row_slots = slots + l * cap;
+  int n = counts[l];
+  if (tid < 3) hit_s[tid] = 0;
+  __syncthreads();
+  int it = 0;
+  for (int j = lo; j < hi && n < maxq; ++j) {              // n is uniform over the workgroup; a full label ends the walk
+    const float* __restrict__ c = cand + order[j] * D;
+    // every wave computes the candidate's norm itself (same lanes, same order: the same bits in every wave)
+    const float inv_c = 1.f / fmaxf(sqrtf(bank_dot<VEC4>(c, c, D, lane)), 1e-12f);
+    if (exclude && n > 0) {
+      bool hit = false;
+      if (VEC4 && D == 256) {                              // the candidate in registers, one 16-byte load per lane and bank row
+        const float4_ x = *(const float4_*)(c + lane * 4);
+        for (int r = wave; r < n; r += BANK_WAVES) {
+          const int prow = row_slots[r];
+          const float4_ y = *(const float4_*)(pool + (long)prow * 256 + lane * 4);
+          const float dot = wave_sum(x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3]);
+          hit |= dot * inv_c * inv_norm[prow] > thr;
+        }
+      } else {
+        for (int r = wave; r < n; r += BANK_WAVES) {
+          const int prow = row_slots[r];
+          hit |= bank_dot<VEC4>(c, pool + (long)prow * D, D, lane) * inv_c * inv_norm[prow] > thr;
+        }
+      }
+      const int p = it % 3;
+      if (hit && lane == 0) hit_s[p] = 1;
+      if (tid == 0) hit_s[(it + 1) % 3] = 0;               // last read two barriers ago
+      __syncthreads();
+      ++it;
+      if (hit_s[p]) continue;                              // a similar row is in the bank already
+    }
+    if (tid == 0) prow_s = atomicAdd(&state[0], 1);        // the pool is append-only: one row per admitted candidate
+    __syncthreads();
+    const int prow = prow_s;
+    if (prow >= pool_rows) {                               // the host sized the pool for every candidate of the call: not reached
+      if (tid == 0) state[1] = 1;
+      break;
+    }
+    float* __restrict__ dst = pool + (long)prow * D;
+    if (VEC4) {
+      for (int k = tid * 4; k < D; k += BANK_THREADS * 4) *(float4_*)(dst + k) = *(const float4_*)(c + k);
+    } else {
+      for (int k = tid; k < D; k += BANK_THREADS) dst[k] = c[k];
+    }
+    if (tid == 0) {
+      row_slots[n] = prow;
+      inv_norm[prow] = inv_c;
+    }
+    ++n;
+    __syncthreads();                                       // the row, its slot and its norm before the next candidate's comparisons
+  }
+  if (tid == 0) counts[l] = n;
+}
+
+extern "C" int mq_bank_admit(const float* cand, const long long* sorted_labels, const long long* order, float* pool, float* inv_norm, int* slots,
+                             int* counts, int* state, int N, int D, int pool_rows, int cap, int label_lo, int num_labels, int maxq, int exclude,
+                             float thr, void* stream) {
+  if (N <= 0 || num_labels <= 0) return 0;
+  if (D <= 0 || label_lo < 0 || maxq > cap || pool_rows < 0) return -1;
+  const bool vec4 = D % 4 == 0 && ((uintptr_t)cand | (uintptr_t)pool) % 16 == 0;
+  if (vec4)
+    hipLaunchKernelGGL(bank_admit_kernel<true>, dim3(num_labels), dim3(BANK_THREADS), 0, (hipStream_t)stream, cand, sorted_labels, order, pool,
+                       inv_norm, slots, counts, state, N, D, pool_rows, cap, label_lo, maxq, exclude, thr);
+  else
+    hipLaunchKernelGGL(bank_admit_kernel<false>, dim3(num_labels), dim3(BANK_THREADS), 0, (hipStream_t)stream, cand, sorted_labels, order, pool,
+                       inv_norm, slots, counts, state, N, D, pool_rows, cap, label_lo, maxq, exclude, thr);
+  return (int)hipGetLastError();
+}
+
+#endif
+MQ_NAMESPACE_END

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from .. import ops as _ops
+from ..query_bank import QueryBank
 from ..structures import BoxList, to_image_list
 from . import pipeline
 from .poolers import CustomPooler, Pooler
@@ -67,6 +68,9 @@ def pool_into_bank(cfg, pooler, visual_features, targets, query_images, exclude_
     assert len(labels) == len(query_feats)
     max_query_number = cfg.VISION_QUERY.MAX_QUERY_NUMBER if max_query_number is None else max_query_number
     thr = cfg.VISION_QUERY.SIMILARITY_THRESHOLD
+    if isinstance(query_images, QueryBank):                                         # device-resident bank: the whole loop below in one launch
+        query_images.update(query_feats, labels, max_query_number, exclude_similar, thr)
+        return query_images
     for label, feat in zip(labels.tolist(), query_feats):
         cur = query_images[label] if (label in query_images or hasattr(query_images, "default_factory")) else []
         n = len(cur)

@@ -72,6 +72,7 @@ _SIGNATURES = {
     "mq_tta_merge_finalize": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
     "mq_lvis_match": (_i, [_vp] * 13 + [_i, _l, _vp]),
     "mq_lvis_accumulate": (_i, [_vp] * 7 + [_i, _vp]),
+    "mq_bank_admit": (_i, [_vp] * 8 + [_i] * 8 + [_f, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
@@ -1594,3 +1595,22 @@ def lvis_accumulate(cat_off, order, dt_bits, num_gt, rec_thr, n_thr=10):
         _chk(lib.mq_lvis_accumulate(_ptr(cat_off), _ptr(order), _ptr(dt_bits), _ptr(num_gt), _ptr(rec_thr), _ptr(precision), _ptr(recall), K,
                                     _stream()), "mq_lvis_accumulate")
     return precision, recall
+
+
+# ---- vision-query bank (csrc/query_bank.hip; host side: mq_det_amd/query_bank.py QueryBank)
+def bank_admit(cand, sorted_labels, order, pool, inv_norm, slots, counts, state, label_lo, num_labels, maxq, exclude, thr):
+    """The admission loop for every candidate row of `cand` [N, D] (in place on pool / inv_norm / slots / counts / state).  Layouts:
+    include/mqdet_hip.h mq_bank_admit.  The caller has sized the pool for N more rows and the label table for label_lo + num_labels labels."""
+    lib = load_library()
+    _need_gpu(cand, sorted_labels, order, pool, inv_norm, slots, counts, state)
+    assert cand.dtype == pool.dtype == inv_norm.dtype == torch.float32 and sorted_labels.dtype == order.dtype == torch.int64
+    assert slots.dtype == counts.dtype == state.dtype == torch.int32 and state.numel() == 2
+    for t in (cand, sorted_labels, order, pool, inv_norm, slots, counts, state):
+        assert t.is_contiguous()
+    N, D = cand.shape
+    R, cap = pool.shape[0], slots.shape[1]
+    assert len(sorted_labels) == len(order) == N and pool.numel() == R * D and len(inv_norm) == R and len(counts) == slots.shape[0]
+    assert 0 <= label_lo and label_lo + num_labels <= len(counts) and 0 < maxq <= cap
+    with _timed("bank_admit"):
+        _chk(lib.mq_bank_admit(_ptr(cand), _ptr(sorted_labels), _ptr(order), _ptr(pool), _ptr(inv_norm), _ptr(slots), _ptr(counts), _ptr(state),
+                               N, D, R, cap, int(label_lo), int(num_labels), int(maxq), int(bool(exclude)), float(thr), _stream()), "mq_bank_admit")
