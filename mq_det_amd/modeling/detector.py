@@ -10,19 +10,17 @@ Differences by design: fp16 compute on MI355X HIP kernels; B > 1 is allowed with
 reference asserts B == 1, :354); post-processing has a single device->host sync per forward.
 """
 import os
-from collections import OrderedDict
 
 import torch
-from torch import nn
 
 from .. import ops as _ops
 from ..query_bank import QueryBank
 from ..structures import BoxList, to_image_list
 from . import pipeline
-from .poolers import CustomPooler, Pooler
-from .graph_runner import GraphRunner, memoised
+from .device_model import DeviceModel, compute_dtype  # noqa: F401  (compute_dtype: re-exported)
+from .graph_runner import Memo
 from .params import Container, build_param_tree
-from .query_selector import QuerySelector, labels_and_maps, build_token_index
+from .query_selector import build_token_index, prepare_positive_map
 
 
 def expand_bbox(box_list, expand_ratio=1.5):
@@ -37,21 +35,6 @@ def expand_bbox(box_list, expand_ratio=1.5):
         nb.add_field("labels", boxes.get_field("labels"))
         out.append(nb.clip_to_image(remove_empty=True))
     return out
-
-
-def compute_dtype(cfg):
-    """MODEL.COMPUTE_DTYPE: the operand type of every kernel on the path -- "float16" (default, BASELINE.json configs[1]),
-    "bfloat16" (configs[3]: the *_bf16 entry points of include/mqdet_hip.h) or "float32" (the precise mode: the *_f32 entry points, the
-    same kernel sources with fp32 operands, and fp32 library GEMMs -- a quarter of the MFMA rate, for parity at the north-star's 1e-3 end
-    to end, not for throughput); accumulation and residual streams are fp32 in every mode."""
-    name = str(cfg.MODEL.get("COMPUTE_DTYPE", "float16")).lower()
-    if name in ("float16", "fp16", "half"):
-        return torch.float16
-    if name in ("bfloat16", "bf16"):
-        return torch.bfloat16
-    if name in ("float32", "fp32", "float"):
-        return torch.float32
-    raise NotImplementedError(f"MODEL.COMPUTE_DTYPE = {name}: float16, bfloat16 or float32")
 
 
 def pool_into_bank(cfg, pooler, visual_features, targets, query_images, exclude_similar, max_query_number):
@@ -86,38 +69,24 @@ def pool_into_bank(cfg, pooler, visual_features, targets, query_images, exclude_
     return query_images
 
 
-class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
+class GeneralizedVLRCNN_New(DeviceModel):
+    _plan_memos = ("_anchor_cache", "_front_cache")
+
     def __init__(self, cfg, tokenizer=None, **kwargs):
-        super().__init__()
-        self.cfg = cfg
+        super().__init__(cfg)
         for name in ("backbone", "language_backbone", "rpn"):
             self.add_module(name, Container())
         build_param_tree(self, cfg)
         self.roi_heads = None                                     # RPN_ONLY (roi_heads/__init__.py:64-84)
-        # box pooler of the query-extraction path (generalized_vl_rcnn_new.py:107-121)
-        RB = cfg.MODEL.ROI_BOX_HEAD
-        pool_cls = Pooler if cfg.VISION_QUERY.SELECT_FPN_LEVEL else CustomPooler
-        self.pooler = pool_cls(output_size=(RB.POOLER_RESOLUTION, RB.POOLER_RESOLUTION), scales=RB.POOLER_SCALES,
-                               sampling_ratio=RB.POOLER_SAMPLING_RATIO, use_v2=True)
-        self.query_selector = None if cfg.VISION_QUERY.DISABLE_SELECTOR else QuerySelector(cfg)
+        self._build_query_path()
         self.tokenizer = tokenizer if tokenizer is not None else self._load_tokenizer(cfg)
-        self._plan = None
-        self._plan_key = None
-        self._kernels = None                                      # kernel selection of the plan (ops.configure), set by prepare()
-        self._anchor_cache = {}
-        self._graphs = OrderedDict()                              # LRU of captured HIP graphs, keyed by static shapes only
-        self._graph_pool = None                                   # one memory pool shared by every captured graph
-        self._tok_cache, self._tokidx_cache, self._wh_cache, self._live_cache = {}, {}, {}, {}
-        self._feat_cache = None                                   # Swin + FPN + pooled tokens of the last image batch (f1)
-        self._front_cache = OrderedDict()                         # image-independent BERT layers per caption (f1)
-        self.use_hip_graph = bool(cfg.MODEL.get("USE_HIP_GRAPH", True))
+        self._anchor_cache = Memo(8)                              # keyed by feature-map geometry: a handful is live at once
+        # host memos of a caption / an image-size list; their tensors are registered with memoised(): a graph replay skips copying them
+        self._tok_cache, self._tokidx_cache, self._wh_cache, self._live_cache = (Memo(256, memoise=True) for _ in range(4))
+        self._front_cache = Memo(cfg.MODEL.get("LANG_FRONT_CACHE", 64))   # image-independent BERT layers per caption (f1)
         # lanes of the staggered schedule (_staggered_program); 1 = the whole batch as one lane.  MQ_MICRO_BATCHES overrides (A/B runs)
         self.micro_batches = int(os.environ.get("MQ_MICRO_BATCHES", cfg.MODEL.get("MICRO_BATCHES", 1)))
-        self.graph_cache_size = int(cfg.MODEL.get("HIP_GRAPH_CACHE", 8))
-        self.graph_warm_calls = int(cfg.MODEL.get("HIP_GRAPH_WARM_CALLS", 1))
-        self.backbone_cache = bool(cfg.MODEL.get("BACKBONE_CACHE", True))
-        self.cache_stats = {"backbone_hit": 0, "backbone_miss": 0, "front_hit": 0, "front_miss": 0,
-                            "graph_replay": 0, "graph_capture": 0, "eager": 0, "graph_evict": 0}
+        self.cache_stats.update(front_hit=0, front_miss=0)
         self.eval()
 
     @staticmethod
@@ -131,36 +100,8 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
                 "(mq_det_amd.utils.tokenizer.build_synthetic_tokenizer writes one) or pass tokenizer=...")
         return AutoTokenizer.from_pretrained(name)
 
-    # ------------------------------------------------------------------ plan management
-    def _invalidate(self):
-        self._plan = None
-        self._anchor_cache = {}
-        self._drop_graphs()
-        self._feat_cache = None
-        self._front_cache = OrderedDict()
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        self._invalidate()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._invalidate()
-        return out
-
-    def prepare(self, device=None):
-        """(Re)build the fp16 inference plan on `device`.  Called lazily by forward."""
-        device = torch.device(device) if device is not None else next(self.parameters()).device
-        if device.type != "cuda":
-            raise RuntimeError("mq_det_amd runs on MI355X only (HIP kernels, no CPU fallback); got device " + str(device))
-        from .. import ops
-        ops.load_library()
-        self._kernels = dict(ops.configure(self.cfg))              # kernel selection: read once per plan, kept WITH the plan
-        self._validate_config()
-        self._plan = pipeline.build_plan(self.state_dict(), self.cfg, device, dtype=compute_dtype(self.cfg))
-        self._plan_key = device
-        return self._plan
+    def _build_plan(self, device, dtype):
+        return pipeline.build_plan(self.state_dict(), self.cfg, device, dtype=dtype)
 
     def _validate_config(self):
         """Fail early, with the config key named, on settings of the reference this path does not implement (instead of a
@@ -188,14 +129,6 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
             raise NotImplementedError("VISION_QUERY.ADD_ADAPT_LAYER / QUERY_FUSION / AUGMENT_IMAGE_WITH_QUERY are not implemented")
 
     # ------------------------------------------------------------------ reference API
-    def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("mq_det_amd implements the inference forward only (north-star scope)")
-        return super().train(False)
-
-    def load_query_bank(self, query_path):
-        self.query_selector.load_query_bank(query_path)
-
     @torch.no_grad()
     def extract_query(self, images=None, targets=None, query_images=None, visual_features=None, exclude_similar=False,
                       device=None, max_query_number=None):
@@ -211,28 +144,17 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
         targets = expand_bbox([t.to(device) for t in targets if t is not None], expand_ratio=cfg.VISION_QUERY.EXPAND_RATIO)
         if visual_features is None:
             images = to_image_list(images)
-            if self._plan is None or self._plan_key != images.tensors.device:
-                self.prepare(images.tensors.device)
-            _ops.activate(self._kernels)
-            dtype = self._plan["backbone.body.patch_embed.proj.weight"].dtype
+            dtype = self._ensure_plan(images.tensors.device)["backbone.body.patch_embed.proj.weight"].dtype
             x = images.tensors.to(dtype).contiguous(memory_format=torch.channels_last)
             visual_features, _ = self._backbone_stage(x)
         else:
             visual_features = [v.to(device) for v in visual_features]
         return pool_into_bank(cfg, self.pooler, visual_features, targets, query_images, exclude_similar, max_query_number)
 
-    def flatten_fpn_features(self, features):
-        return pipeline.pooled_fpn_tokens(features)
-
-    def get_labels_and_maps_from_positive_map(self, positive_map, dtype=torch.float):
-        return labels_and_maps(positive_map, self.cfg.MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN)
-
     def tokenize(self, captions, device):
         """HF tokenizer on the host (generalized_vl_rcnn_new.py:378-383); memoised per caption tuple -- the LVIS
         protocol re-sends the same 31 chunk captions for every image (engine/inference.py:605-625)."""
-        key = (tuple(captions), str(device))
-        hit = self._tok_cache.get(key)
-        if hit is None:
+        def make():
             LB = self.cfg.MODEL.LANGUAGE_BACKBONE
             # PAD_MAX = False ("longest" in the reference, generalized_vl_rcnn_new.py:378-383) pads to MAX_QUERY_LEN here as well:
             # padded positions are masked keys everywhere (BERT, GCP, VLFuse) and never scored, so the detections are the same;
@@ -243,11 +165,8 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
             # host-side bound of the per-caption key length (last attended position + 1): picks the kernel variant of
             # the VLFuse image-side attention, and is part of the HIP-graph key
             max_kv = int((am * torch.arange(1, am.shape[1] + 1)).max())
-            hit = (memoised(tok["input_ids"].to(device)), memoised(am.to(device)), max_kv)
-            if len(self._tok_cache) > 256:
-                self._tok_cache.clear()
-            self._tok_cache[key] = hit
-        return hit
+            return tok["input_ids"].to(device), am.to(device), max_kv
+        return self._tok_cache.get((tuple(captions), str(device)), make)
 
     def _live_len(self, T, max_kv):
         """Text positions the device programs run on: 16 ceil(max_kv / 16) (the key-block granularity of the attention kernels; VLFuse takes
@@ -263,16 +182,20 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
     def _live_slice(self, input_ids, attention_mask, Tl, cap_key, dev):
         """input_ids / attention_mask cut to their first Tl columns as contiguous tensors (memoised per caption: the HIP-graph replay copies
         its inputs into static buffers, the same two tensors serve every call of a caption)."""
-        key = (cap_key, Tl, str(dev)) if cap_key is not None else None
-        hit = self._live_cache.get(key) if key is not None else None
-        if hit is None:
-            hit = (input_ids[:, :Tl].contiguous(), attention_mask[:, :Tl].contiguous())
-            if key is not None:
-                memoised(hit)
-                if len(self._live_cache) > 256:
-                    self._live_cache.clear()
-                self._live_cache[key] = hit
-        return hit
+        def make():
+            return input_ids[:, :Tl].contiguous(), attention_mask[:, :Tl].contiguous()
+        return make() if cap_key is None else self._live_cache.get((cap_key, Tl, str(dev)), make)
+
+    def _im_wh(self, images, dev):
+        """[B, 2] fp32 (width, height) of every image, memoised per size list."""
+        return self._wh_cache.get((tuple(images.image_sizes), str(dev)), lambda: torch.tensor(
+            [[w, h] for (h, w) in images.image_sizes], dtype=torch.float32, device=dev))
+
+    def _anchors(self, feats):
+        """Anchors of the five levels: constant per feature-map geometry (and plan)."""
+        sizes = tuple(tuple(f.shape[-2:]) for f in feats)
+        return self._anchor_cache.get(sizes, lambda: pipeline.grid_anchors(self._plan, sizes, self.cfg.MODEL.RPN.ANCHOR_STRIDE,
+                                                                            feats[0].device))
 
     @staticmethod
     def _pad_raw_text(raw, T):
@@ -309,10 +232,6 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
         pooled = pipeline.pooled_fpn_tokens(feats) if self._use_vq() else None
         return feats, pooled
 
-    def _use_vq(self):
-        return bool(self.cfg.VISION_QUERY.ENABLED and self.query_selector is not None
-                    and self.query_selector.query_bank is not None)
-
     def _head_stage(self, feats, pooled, front, input_ids, attention_mask, vision, idx, tokidx, label_ids, im_wh, max_kv,
                     want_raw=False):
         """Image-dependent half of the language backbone (pre-select + GCP / BERT layers), VLDyHead, post-processing."""
@@ -324,10 +243,7 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
         lang["max_kv"] = max_kv
         trace = [] if want_raw else None                          # raw mode: per-layer tensors, single-stream schedule
         head = pipeline.vldyhead(P, cfg, feats, lang, trace=trace)
-        sizes = tuple(tuple(f.shape[-2:]) for f in feats)
-        if sizes not in self._anchor_cache:                       # constant per feature-map geometry
-            self._anchor_cache[sizes] = pipeline.grid_anchors(P, sizes, cfg.MODEL.RPN.ANCHOR_STRIDE, feats[0].device)
-        anchors = self._anchor_cache[sizes]
+        anchors = self._anchors(feats)
         post = pipeline.postprocess(cfg, head, anchors, im_wh, tokidx, label_ids, want_cls=want_raw)
         if want_raw:
             return {"post": post, "head": head, "head_trace": trace, "lang": lang, "feats": feats, "anchors": anchors,
@@ -427,10 +343,7 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
                                                       want_gates=False, front=fronts[m], max_kv=max_kv)
                 langs[m]["max_kv"] = max_kv
             hold.append((f, pooled, fronts[m], langs[m]))
-        sizes = tuple(tuple(t.shape[-2:]) for t in feats[0])
-        if sizes not in self._anchor_cache:
-            self._anchor_cache[sizes] = pipeline.grid_anchors(P, sizes, cfg.MODEL.RPN.ANCHOR_STRIDE, dev)
-        anchors = self._anchor_cache[sizes]
+        anchors = self._anchors(feats[0])
         for m in range(n):
             main.wait_stream(Ls[m])
             head = pipeline.vldyhead(P, cfg, feats[m], langs[m])
@@ -463,9 +376,8 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
 
     def clear_caches(self):
         """Drop the per-image feature cache, the per-caption language cache and every captured graph."""
-        self._feat_cache = None
-        self._front_cache = OrderedDict()
-        self._drop_graphs()
+        super().clear_caches()
+        self._front_cache.clear()
 
     @torch.no_grad()
     def forward(self, images, targets=None, captions=None, positive_map=None, greenlight_map=None,
@@ -479,10 +391,7 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
             raise NotImplementedError("training forward is out of scope")
         images = to_image_list(images)
         dev = images.tensors.device
-        if self._plan is None or self._plan_key != dev:
-            self.prepare(dev)
-        _ops.activate(self._kernels)
-        P, cfg = self._plan, self.cfg
+        P, cfg = self._ensure_plan(dev), self.cfg
         dtype = P["backbone.body.patch_embed.proj.weight"].dtype
         Bn = images.tensors.shape[0]
         if input_ids is None:
@@ -493,18 +402,9 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
             cap_key = None
         T = input_ids.shape[1]
 
-        # host-side glue: all memoised, no device sync.  Token positions that the tokenizer's truncation to MAX_QUERY_LEN cut
-        # away cannot be scored (the reference indexes a [L, T] map with them, generalized_vl_rcnn_new.py:295-305): dropped
-        if any(t >= T for v in positive_map.values() for t in (v if not isinstance(v, int) else [v])):
-            positive_map = {k: [t for t in (v if not isinstance(v, int) else [v]) if t < T] for k, v in positive_map.items()}
-        labels_in_caption = [k for k, v in positive_map.items() if len(v) != 0]
-        pm_key = tuple((k, tuple(positive_map[k])) for k in labels_in_caption)
+        # host-side glue: all memoised, no device sync
         onehot = str(cfg.MODEL.DYHEAD.get("SCORE_AGG", "MEAN")).upper() == "ONEHOT"
-        if max_kv > 0:
-            # the alignment kernel scores text columns below 16 ceil(max_kv / 16) only: a positive_map that names a token behind the
-            # caption's last live one (abnormal, but legal for the reference, which scores all T columns) widens the bound instead of
-            # being scored as 0 inside a MEAN
-            max_kv = max(max_kv, len(positive_map) if onehot else 1 + max((t for k in labels_in_caption for t in positive_map[k]), default=-1))
+        positive_map, labels_in_caption, pm_key, score_map, score_labels, max_kv = prepare_positive_map(positive_map, T, max_kv, onehot)
         # LIVE-ROW COMPACTION (round 5): everything behind the tokenizer runs on the first Tl = 16 ceil(max_kv / 16) text positions instead of
         # the MAX_QUERY_LEN = 256 the caption is padded to.  Padded positions are masked KEYS everywhere (BERT, GCP, VLFuse) and are never
         # scored, so no live output depends on them -- but as ROWS they went through every text-side GEMM, LayerNorm and elementwise kernel
@@ -517,65 +417,40 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
             vision, idx = self.query_selector.select_cached(pm_key, labels_in_caption, positive_map, Bn, Tl, dev, dtype)
             if vision.shape[1] == 0:                              # no label of this caption has a vision query: text only
                 vision = idx = None
-        tk = (len(positive_map), "onehot", str(dev)) if onehot else (pm_key, str(dev))
-        hit = self._tokidx_cache.get(tk)
-        if hit is None:
-            if len(self._tokidx_cache) > 256:
-                self._tokidx_cache.clear()
-            if onehot:      # scores = logits[:, :, :len(positive_map)] (rpn/inference.py:789-791): class column j is token j, label j + 1
-                n = len(positive_map)
-                hit = build_token_index({j + 1: [j] for j in range(n)}, list(range(1, n + 1)), dev)
-            else:
-                hit = build_token_index(positive_map, labels_in_caption, dev)
-            self._tokidx_cache[tk] = memoised(hit)
-        tokidx, label_ids = hit
-        wh_key = (tuple(images.image_sizes), str(dev))
-        im_wh = self._wh_cache.get(wh_key)
-        if im_wh is None:
-            if len(self._wh_cache) > 256:
-                self._wh_cache.clear()
-            im_wh = self._wh_cache[wh_key] = memoised(torch.tensor([[w, h] for (h, w) in images.image_sizes],
-                                                                   dtype=torch.float32, device=dev))
+        tokidx, label_ids = self._tokidx_cache.get((len(score_labels), "onehot", str(dev)) if onehot else (pm_key, str(dev)),
+                                                   lambda: build_token_index(score_map, score_labels, dev))
+        im_wh = self._im_wh(images, dev)
         tail = (input_ids, attention_mask, vision, idx, tokidx, label_ids, im_wh, max_kv)
         if return_raw:
             x = images.tensors.to(dtype).contiguous(memory_format=torch.channels_last)
             raw = self._full_program(x, *tail, want_raw=True)
             return self._pad_raw_text(raw, T) if Tl < T else raw
-        from .. import ops
-        use_graph = self.use_hip_graph and not ops.timing_active()
+        use_graph = self.use_hip_graph and not _ops.timing_active()
 
         # f1: the pixels of the previous call (same tensor object, not modified since) -> cached Swin / FPN features;
-        # a caption seen before -> cached image-independent BERT layers.  The strong reference to the input tensor keeps
-        # its storage alive, so object identity + version counter cannot alias a different batch.
-        fc = self._feat_cache if (self.backbone_cache and reuse_backbone is not False) else None
+        # a caption seen before -> cached image-independent BERT layers
         src = images.tensors
-        if fc is not None and fc["src"] is src and fc["version"] == src._version and (vision is None or fc["pooled"] is not None):
-            self.cache_stats["backbone_hit"] += 1
-            fkey = (cap_key, Bn, vision is not None, Tl)
-            front = self._front_cache.get(fkey) if cap_key is not None else None
-            if front is None:
-                self.cache_stats["front_miss"] += 1
-                front = pipeline.language_front(P, cfg, input_ids, attention_mask, vision is not None, max_kv=max_kv)
-                if cap_key is not None:
-                    self._front_cache[fkey] = front
-                    while len(self._front_cache) > int(cfg.MODEL.get("LANG_FRONT_CACHE", 64)):
-                        self._front_cache.popitem(last=False)
-            else:
-                self.cache_stats["front_hit"] += 1
-                self._front_cache.move_to_end(fkey)
-            out = self._run("_rest_program", (fc["feats"], fc["pooled"], front) + tail, use_graph)
-        else:
+        fkey = (cap_key, Bn, vision is not None, Tl)
+        out = None
+
+        def full():                                               # miss: the whole device forward; the caches keep CLONES of its features
+            nonlocal out                                          # (under HIP-graph replay `out` are the graph's static buffers)
             x = self._pixels(src, dtype)
             staggered = (self.micro_batches > 1 and Bn > 1 and not self.backbone_cache and x.is_cuda
                          and not cfg.VISION_QUERY.RETURN_ATTN_GATE_VALUE and not return_backbone_features
                          and cfg.MODEL.DYHEAD.get("LEVEL_STREAMS", True))
             out = self._run("_staggered_program" if staggered else "_full_program", (x,) + tail, use_graph)
-            if self.backbone_cache:
-                self.cache_stats["backbone_miss"] += 1
-                keep = self._tree_map(lambda t: t.clone(), {"feats": out["feats"], "pooled": out["pooled"], "front": out["front"]})
-                self._feat_cache = {"src": src, "version": src._version, "feats": keep["feats"], "pooled": keep["pooled"]}
-                if cap_key is not None:
-                    self._front_cache[(cap_key, Bn, vision is not None, Tl)] = keep["front"]
+            if not self.backbone_cache:
+                return None
+            keep = self._tree_map(lambda t: t.clone(), {"feats": out["feats"], "pooled": out["pooled"], "front": out["front"]})
+            if cap_key is not None:
+                self._front_cache.get(fkey, lambda: keep["front"])
+            return {"feats": keep["feats"], "pooled": keep["pooled"]}
+        fc, hit = self._cached_features(src, reuse_backbone, full)
+        if hit:
+            front = self._front(fkey if cap_key is not None else None, lambda: pipeline.language_front(
+                P, cfg, input_ids, attention_mask, vision is not None, max_kv=max_kv))
+            out = self._run("_rest_program", (fc["feats"], fc["pooled"], front) + tail, use_graph)
 
         # fixed-shape detections [B, K, 6] for the RCCL all-gather (mq_det_amd.parallel.gather_detections); cloned: under
         # HIP-graph replay `out` are the graph's static buffers, which the next forward overwrites
@@ -611,37 +486,30 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
     # ------------------------------------------------------------------ chunk batching
     def _features(self, images):
         """(feats, pooled) of an image batch through the per-image cache (Swin + FPN run once per distinct tensor)."""
-        dev = images.tensors.device
-        if self._plan is None or self._plan_key != dev:
-            self.prepare(dev)
-        _ops.activate(self._kernels)
+        P = self._ensure_plan(images.tensors.device)
         src = images.tensors
-        fc = self._feat_cache if self.backbone_cache else None
-        if fc is not None and fc["src"] is src and fc["version"] == src._version and (fc["pooled"] is not None or not self._use_vq()):
-            self.cache_stats["backbone_hit"] += 1
-            return fc["feats"], fc["pooled"]
-        self.cache_stats["backbone_miss"] += 1
-        dtype = self._plan["backbone.body.patch_embed.proj.weight"].dtype
-        x = self._pixels(src, dtype)
-        feats, pooled = self._backbone_stage(x)
-        if self.backbone_cache:
-            self._feat_cache = {"src": src, "version": src._version, "feats": feats, "pooled": pooled}
-        return feats, pooled
+
+        def make():
+            feats, pooled = self._backbone_stage(self._pixels(src, P["backbone.body.patch_embed.proj.weight"].dtype))
+            return {"feats": feats, "pooled": pooled}
+        fc, _ = self._cached_features(src, None, make)
+        return fc["feats"], fc["pooled"]
+
+    def _features_usable(self, rec):
+        """Features cached before a query bank was loaded lack the pooled FPN tokens the GCP pre-select attends to."""
+        return rec["pooled"] is not None or not self._use_vq()
+
+    def _front(self, key, make):
+        """Image-independent BERT layers of a caption through their cache (`key` None: caller-supplied token ids, not cached)."""
+        self.cache_stats["front_hit" if key is not None and key in self._front_cache else "front_miss"] += 1
+        return make() if key is None else self._front_cache.get(key, make)
 
     def _front_for(self, caption, dev, use_vq):
         """Image-independent BERT layers of ONE caption (batch 1), cached per caption."""
-        key = ((caption,), 1, use_vq)
-        fr = self._front_cache.get(key)
-        if fr is None:
-            self.cache_stats["front_miss"] += 1
+        def make():
             ids, am, kv = self.tokenize([caption], dev)
-            fr = self._front_cache[key] = pipeline.language_front(self._plan, self.cfg, ids, am, use_vq, max_kv=kv)
-            while len(self._front_cache) > int(self.cfg.MODEL.get("LANG_FRONT_CACHE", 64)):
-                self._front_cache.popitem(last=False)
-        else:
-            self.cache_stats["front_hit"] += 1
-            self._front_cache.move_to_end(key)
-        return fr
+            return pipeline.language_front(self._plan, self.cfg, ids, am, use_vq, max_kv=kv)
+        return self._front(((caption,), 1, use_vq), make)
 
     @torch.no_grad()
     def forward_chunks(self, images, chunks, max_items=32):
@@ -660,28 +528,24 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
         dtype = P["backbone.body.patch_embed.proj.weight"].dtype
         Bn = images.tensors.shape[0]
         use_vq = self._use_vq()
-        from .. import ops
-        use_graph = self.use_hip_graph and not ops.timing_active()
-        im_wh = torch.tensor([[w, h] for (h, w) in images.image_sizes], dtype=torch.float32, device=dev)
+        use_graph = self.use_hip_graph and not _ops.timing_active()
+        im_wh = self._im_wh(images, dev)
+        onehot = str(cfg.MODEL.DYHEAD.get("SCORE_AGG", "MEAN")).upper() == "ONEHOT"
         results = []
         per = max(1, int(max_items) // Bn)
         for g0 in range(0, len(chunks), per):
             grp = chunks[g0:g0 + per]
             g = len(grp)
-            ids, ams, kvs, fronts, pms, labs = [], [], [], [], [], []
+            ids, ams, kvs, fronts, pms, labs, smaps = [], [], [], [], [], [], []
             for cap, pm in grp:
                 i, a, kv = self.tokenize([cap], dev)
-                T = i.shape[1]
-                if any(t >= T for v in pm.values() for t in (v if not isinstance(v, int) else [v])):
-                    pm = {k: [t for t in (v if not isinstance(v, int) else [v]) if t < T] for k, v in pm.items()}
+                pm, lab, _, smap, slab, kv = prepare_positive_map(pm, i.shape[1], kv, onehot)
                 ids.append(i)
                 ams.append(a)
-                kv_pm = max(kv, 1 + max((t for v in pm.values() for t in (v if not isinstance(v, int) else [v])), default=-1))
-                if str(cfg.MODEL.DYHEAD.get("SCORE_AGG", "MEAN")).upper() == "ONEHOT":
-                    kv_pm = max(kv_pm, len(pm))                   # class column j scores token j (forward() widens the same way)
-                kvs.append(min(kv_pm, T) if kv > 0 else kv)
+                kvs.append(kv)
                 pms.append(pm)
-                labs.append([k for k, v in pm.items() if len(v) != 0])
+                labs.append(lab)
+                smaps.append((smap, slab))                        # what the scoring kernel takes (ONEHOT: class column j = token j, label j + 1)
             T = self._live_len(ids[0].shape[1], max(kvs) if min(kvs) > 0 else 0)          # live-row compaction (see forward): the group's longest caption
             live = lambda t_: t_[:, :T]                           # noqa: E731
             ids, ams = [live(i) for i in ids], [live(a) for a in ams]
@@ -700,10 +564,6 @@ class GeneralizedVLRCNN_New(GraphRunner, nn.Module):
                      "hidden": [rep(torch.cat([live(f["hidden"][k]) for f in fronts])) for k in range(len(fronts[0]["hidden"]))],
                      "key_bias": rep(torch.cat([live(f["key_bias"]) for f in fronts])), "kv_len": rep(torch.cat([f["kv_len"] for f in fronts])),
                      "next": fronts[0]["next"]}
-            if str(cfg.MODEL.DYHEAD.get("SCORE_AGG", "MEAN")).upper() == "ONEHOT":      # class column j = token j, label j + 1
-                smaps = [({j + 1: [j] for j in range(min(len(pm), T))}, list(range(1, min(len(pm), T) + 1))) for pm in pms]
-            else:
-                smaps = list(zip(pms, labs))
             L = max(1, max(len(l) for _, l in smaps))
             MT = max(1, max((len(pm[k]) for pm, l in smaps for k in l), default=1))
             tok3 = torch.full((g, L, MT), -1, dtype=torch.int32)

@@ -9,19 +9,17 @@ Differences by design: vision queries work for any batch size whose images share
 :502); a label with an empty token list silences ALL detections exactly like the reference's NaN propagation (:291-305).
 """
 import os
-from collections import OrderedDict
 
 import torch
-from torch import nn
 
 from .. import ops as _ops
 from ..structures import BoxList, to_image_list
-from . import gdino_pipeline as gp
-from .detector import compute_dtype, expand_bbox, pool_into_bank
-from .graph_runner import GraphRunner
+from . import gdino_pipeline as gp, pipeline
+from .detector import expand_bbox, pool_into_bank
+from .device_model import DeviceModel
+from .graph_runner import Memo
 from .params import build_param_tree, gdino_param_specs, gdino_swin_cfg
-from .poolers import CustomPooler, Pooler
-from .query_selector import QuerySelector, labels_and_maps
+from .query_selector import prepare_positive_map
 
 
 def preprocess_caption(caption):
@@ -30,33 +28,21 @@ def preprocess_caption(caption):
     return result if result.endswith(".") else result + "."
 
 
-class GroundingDINO(GraphRunner, nn.Module):
+class GroundingDINO(DeviceModel):
+    _plan_memos = ("_geo_cache",)
+
     def __init__(self, cfg, tokenizer=None, **kwargs):
-        super().__init__()
-        self.cfg = cfg
+        super().__init__(cfg)
         G = cfg.GROUNDINGDINO
         self._validate_config()
         build_param_tree(self, cfg, specs=gdino_param_specs(cfg))
         self.box_threshold = G.box_threshold
         self.num_queries, self.hidden_dim, self.max_text_len = G.num_queries, G.hidden_dim, 256
-        RB = cfg.MODEL.ROI_BOX_HEAD
-        pool_cls = Pooler if cfg.VISION_QUERY.SELECT_FPN_LEVEL else CustomPooler
-        self.pooler = pool_cls(output_size=(RB.POOLER_RESOLUTION, RB.POOLER_RESOLUTION), scales=RB.POOLER_SCALES,
-                               sampling_ratio=RB.POOLER_SAMPLING_RATIO, use_v2=True)
-        self.query_selector = None if cfg.VISION_QUERY.DISABLE_SELECTOR else QuerySelector(cfg)
+        self._build_query_path()
         self.tokenizer = tokenizer if tokenizer is not None else self._load_tokenizer(G.text_encoder_type)
         self.specical_tokens = self.tokenizer.convert_tokens_to_ids(["[CLS]", "[SEP]", ".", "?"])      # (sic) groundingdino.py:194
         self._swin = gdino_swin_cfg(cfg)
-        self._plan = self._plan_key = None
-        self._kernels = None                                      # kernel selection of the plan (ops.configure), set by prepare()
-        self._graphs = OrderedDict()
-        self._geo_cache, self._txt_cache, self._map_cache = OrderedDict(), OrderedDict(), OrderedDict()
-        self._feat_cache = None                                   # projected levels of the last image batch
-        self.backbone_cache = bool(cfg.MODEL.get("BACKBONE_CACHE", True))
-        self.use_hip_graph = bool(cfg.MODEL.get("USE_HIP_GRAPH", True))
-        self.graph_cache_size = int(cfg.MODEL.get("HIP_GRAPH_CACHE", 8))
-        self.graph_warm_calls = int(cfg.MODEL.get("HIP_GRAPH_WARM_CALLS", 1))
-        self.cache_stats = {"graph_replay": 0, "graph_capture": 0, "eager": 0, "graph_evict": 0, "backbone_hit": 0, "backbone_miss": 0}
+        self._geo_cache, self._txt_cache, self._map_cache = Memo(16), Memo(64), Memo(64)
         self.eval()
 
     @staticmethod
@@ -86,74 +72,15 @@ class GroundingDINO(GraphRunner, nn.Module):
         if V.get("ADD_ADAPT_LAYER", False) or V.get("QUERY_FUSION", False) or V.get("LEARNABLE_BANK", False):
             raise NotImplementedError("VISION_QUERY.ADD_ADAPT_LAYER / QUERY_FUSION / LEARNABLE_BANK are not implemented")
 
-    # ------------------------------------------------------------------ plan management
-    def _invalidate(self):
-        self._plan = None
-        self._drop_graphs()
-        self._geo_cache = OrderedDict()
-        self._feat_cache = None
-
-    def clear_caches(self):
-        self._feat_cache = None
-        self._drop_graphs()
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        self._invalidate()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._invalidate()
-        return out
-
-    def prepare(self, device=None):
-        device = torch.device(device) if device is not None else next(self.parameters()).device
-        if device.type != "cuda":
-            raise RuntimeError("mq_det_amd runs on MI355X only (HIP kernels, no CPU fallback); got device " + str(device))
-        from .. import ops
-        ops.load_library()
-        self._kernels = dict(ops.configure(self.cfg))              # kernel selection: read once per plan, kept WITH the plan
-        self._plan = gp.build_gdino_plan(self.state_dict(), self.cfg, device, self._swin, dtype=compute_dtype(self.cfg))
-        self._plan_key = device
-        return self._plan
-
-    def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("mq_det_amd implements the inference forward only (north-star scope)")
-        return super().train(False)
-
-    def load_query_bank(self, query_path):
-        self.query_selector.load_query_bank(query_path)
-
-    def _use_vq(self):
-        return bool(self.cfg.VISION_QUERY.ENABLED and self.query_selector is not None
-                    and self.query_selector.query_bank is not None)
-
-    def flatten_fpn_features(self, features):
-        from . import pipeline
-        return pipeline.pooled_fpn_tokens(features)
-
-    def get_labels_and_maps_from_positive_map(self, positive_map, dtype=torch.float):
-        return labels_and_maps(positive_map, self.cfg.MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN)
+    def _build_plan(self, device, dtype):
+        return gp.build_gdino_plan(self.state_dict(), self.cfg, device, self._swin, dtype=dtype)
 
     # ------------------------------------------------------------------ memoised host-side glue
-    @staticmethod
-    def _memo(cache, key, make, cap=64):
-        hit = cache.get(key)
-        if hit is None:
-            hit = cache[key] = make()
-            while len(cache) > cap:
-                cache.popitem(last=False)
-        else:
-            cache.move_to_end(key)
-        return hit
-
     def _text(self, captions, dev):
         def make():
             tok = self.tokenizer(list(captions), padding="max_length", return_tensors="pt")          # groundingdino.py:518
             return gp.text_inputs(self.cfg, tok["input_ids"], tok["attention_mask"], self.specical_tokens, dev)
-        return self._memo(self._txt_cache, (tuple(captions), str(dev)), make)
+        return self._txt_cache.get((tuple(captions), str(dev)), make)
 
     def _class_map(self, positive_map, dev):
         """[T, C] fp32: column label-1 holds 1/len over the label's tokens (convert_grounding_to_od_logits, MEAN);
@@ -173,7 +100,7 @@ class GroundingDINO(GraphRunner, nn.Module):
                 for t in toks:
                     m[t, lab - 1] += 1.0 / len(toks)
             return m.to(dev), empty
-        return self._memo(self._map_cache, key, make)
+        return self._map_cache.get(key, make)
 
     # ------------------------------------------------------------------ device program (capturable)
     def _program(self, x, geo, txt, vision, idx, class_map, im_hw, nan_labels, max_kv=0, trace=None):
@@ -194,31 +121,23 @@ class GroundingDINO(GraphRunner, nn.Module):
         else:
             captions = kw["captions"]
         captions = [preprocess_caption(c) for c in captions]
-        positive_map = kw["positive_map"]
         # token positions cut away by the truncation to max_text_len cannot be scored (the reference would index past the
         # [.., 256] token scores): dropped, like the MQ-GLIP class does
-        T = self.max_text_len
-        if any(t >= T for v in positive_map.values() for t in ([v] if isinstance(v, int) else v)):
-            positive_map = {k: [t for t in ([v] if isinstance(v, int) else v) if t < T] for k, v in positive_map.items()}
+        positive_map, labels_in_caption, pm_key = prepare_positive_map(kw["positive_map"], self.max_text_len)[:3]
         return_backbone_features = kw.get("return_backbone_features", False)
         images = to_image_list(samples)
         dev = images.tensors.device
-        if self._plan is None or self._plan_key != dev:
-            self.prepare(dev)
-        _ops.activate(self._kernels)
-        P = self._plan
+        P = self._ensure_plan(dev)
         dtype = P["backbone.0.patch_embed.proj.weight"].dtype
         Bn, _, H, W = images.tensors.shape
         sizes = tuple((int(h), int(w)) for h, w in images.image_sizes)
-        geo = self._memo(self._geo_cache, (H, W, sizes, str(dev)), lambda: gp.geometry(P, self.cfg, H, W, sizes, dev), cap=16)
+        geo = self._geo_cache.get((H, W, sizes, str(dev)), lambda: gp.geometry(P, self.cfg, H, W, sizes, dev))
         txt, max_kv = self._text(captions, dev)
         class_map, nan_labels = self._class_map(positive_map, dev)
         vision = idx = None
         if self._use_vq():
-            T = self.cfg.MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN
-            labels_in_caption = [k for k, v in positive_map.items() if len(v) != 0]
-            pm_key = tuple((k, tuple(positive_map[k])) for k in labels_in_caption)
-            vision, idx = self.query_selector.select_cached(pm_key, labels_in_caption, positive_map, Bn, T, dev, dtype)
+            vision, idx = self.query_selector.select_cached(pm_key, labels_in_caption, positive_map, Bn,
+                                                            self.cfg.MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN, dev, dtype)
             if vision.shape[1] == 0:
                 vision = idx = None
         im_hw = torch.tensor([[h, w] for (h, w) in sizes], dtype=torch.float32, device=dev)
@@ -229,21 +148,19 @@ class GroundingDINO(GraphRunner, nn.Module):
             out = self._program(*inputs, trace=trace)
             trace.update(out=out, geo=geo, txt=txt)
             return trace
-        from .. import ops
-        use_graph = self.use_hip_graph and not ops.timing_active()
-        # f1: the pixels of the previous call (same tensor object, not modified since) -> cached projected levels; the strong
-        # reference to the input tensor keeps its storage alive, so identity + version counter cannot alias another batch
-        # (a writer that refills `images.tensors` without bumping its version counter must pass reuse_backbone=False -- see
+        use_graph = self.use_hip_graph and not _ops.timing_active()
+        # f1: the pixels of the previous call (same tensor object, not modified since) -> cached projected levels (a writer that
+        # refills `images.tensors` without bumping its version counter must pass reuse_backbone=False -- see
         # GeneralizedVLRCNN_New.forward)
-        fc, src = (self._feat_cache if (self.backbone_cache and kw.get("reuse_backbone") is not False) else None), images.tensors
-        if fc is not None and fc["src"] is src and fc["version"] == src._version:
-            self.cache_stats["backbone_hit"] += 1
-            out = self._run("_program_rest", (fc["src32"],) + inputs[1:], use_graph)
-        else:
+        out = None
+
+        def full():                                               # miss: the whole device forward; the cache keeps a clone of its levels
+            nonlocal out
             out = self._run("_program", inputs, use_graph)
-            if self.backbone_cache:
-                self.cache_stats["backbone_miss"] += 1
-                self._feat_cache = {"src": src, "version": src._version, "src32": out["srcs"].clone()}
+            return out["srcs"].clone() if self.backbone_cache else None
+        src32, hit = self._cached_features(images.tensors, kw.get("reuse_backbone"), full)
+        if hit:
+            out = self._run("_program_rest", (src32,) + inputs[1:], use_graph)
         self.last_packed = packed = out["packed"].clone()
         nz = out["keep"].nonzero()                                 # [n, 2] (image, query) in query order: the one device -> host
         counts = torch.bincount(nz[:, 0], minlength=Bn).tolist()   # sync of the forward
@@ -274,11 +191,7 @@ class GroundingDINO(GraphRunner, nn.Module):
         targets = expand_bbox([t.to(device) for t in targets if t is not None], expand_ratio=cfg.VISION_QUERY.EXPAND_RATIO)
         if visual_features is None:
             images = to_image_list(samples)
-            if self._plan is None or self._plan_key != images.tensors.device:
-                self.prepare(images.tensors.device)
-            _ops.activate(self._kernels)
-            from . import pipeline
-            P = self._plan
+            P = self._ensure_plan(images.tensors.device)
             x = images.tensors.to(P["backbone.0.patch_embed.proj.weight"].dtype).contiguous(memory_format=torch.channels_last)
             src = gp.input_projections(P, cfg, pipeline.swin_forward(P, cfg, x, p="backbone.0", SW=self._swin))
             visual_features, s0 = [], 0

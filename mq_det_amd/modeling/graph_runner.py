@@ -34,6 +34,35 @@ def is_memoised(t):
     return r is not None and r() is t
 
 
+class Memo:
+    """Bounded LRU mapping behind every host-side memo of the detectors: `get(key, make)` returns the stored value (a hit refreshes its recency) or
+    stores `make()` and evicts the oldest entries beyond `capacity`.  `memoise=True` registers the tensors of every stored value with `memoised()`.
+    A full memo drops its OLDEST entry (the dicts it replaces were emptied completely); every value is a pure function of its key, so results
+    cannot depend on what was evicted -- only on whether `make()` runs again."""
+
+    def __init__(self, capacity, memoise=False):
+        self.capacity, self.memoise, self._items = int(capacity), memoise, OrderedDict()
+
+    def get(self, key, make):
+        hit = self._items.get(key)
+        if hit is None:
+            hit = self._items[key] = memoised(make()) if self.memoise else make()
+            while len(self._items) > self.capacity:
+                self._items.popitem(last=False)
+        else:
+            self._items.move_to_end(key)
+        return hit
+
+    def clear(self):
+        self._items.clear()
+
+    def __len__(self):
+        return len(self._items)
+
+    def __contains__(self, key):
+        return key in self._items
+
+
 class GraphRunner:
     """Mixin: expects `self._graphs` (OrderedDict), `self.graph_cache_size`, `self.graph_warm_calls`, `self.cache_stats`."""
 

@@ -33,6 +33,32 @@ def build_token_index(positive_map, labels, device):
     return idx.to(device, non_blocking=True), ids.to(device, non_blocking=True)
 
 
+def prepare_positive_map(positive_map, T, max_kv=0, onehot=False):
+    """What a forward needs from the caller's `{label: [token positions]}` for a caption of T positions; returns
+    (positive_map, labels_in_caption, pm_key, score_map, score_labels, max_kv):
+    - the map with `int` entries listed and positions >= T dropped (the tokenizer's truncation cut them away; the reference would index a
+      [L, T] map with them, generalized_vl_rcnn_new.py:295-305), the labels that keep a token, and a hashable key of the two;
+    - the map and labels the scoring kernel takes: the map itself, or for SCORE_AGG = ONEHOT class column j = token j, label j + 1
+      (`logits[:, :, :len(positive_map)]`, rpn/inference.py:789-791: at most T columns exist);
+    - the key-length bound.  `max_kv <= 0` (unknown) passes through; otherwise it is widened to cover every column that will be scored (the
+      alignment kernel only computes columns below 16 ceil(max_kv / 16): a map that names a token behind the caption's last live one --
+      abnormal, but legal for the reference, which scores all T columns -- must not be scored as 0 inside a MEAN) and clamped to T.
+      Scored columns are 0 .. len(positive_map) - 1 with ONEHOT, else up to the cleaned map's highest token.  A ONEHOT map whose TOKENS lie
+      beyond both the caption's live length and len(positive_map) does not widen the bound: those columns are never scored."""
+    pm = {k: [t for t in ([v] if isinstance(v, int) else v) if t < T] for k, v in positive_map.items()}
+    labels = [k for k, v in pm.items() if len(v) != 0]
+    pm_key = tuple((k, tuple(pm[k])) for k in labels)
+    if onehot:
+        scored = min(len(pm), T)
+        score_map, score_labels = {j + 1: [j] for j in range(scored)}, list(range(1, scored + 1))
+    else:
+        scored = 1 + max((max(pm[k]) for k in labels), default=-1)
+        score_map, score_labels = pm, labels
+    if max_kv > 0:
+        max_kv = min(max(max_kv, scored), T)
+    return pm, labels, pm_key, score_map, score_labels, max_kv
+
+
 class QuerySelector(nn.Module):
     def __init__(self, cfg):
         super().__init__()

@@ -611,3 +611,107 @@ def test_gather_kernels_keep_their_loads_in_flight():
             # one spilled register is reloaded behind the X loads at C = 96 (13 dwords of scratch at the 256-VGPR cap)
             allowed = 3 if "window_attn_qkv" in name else 0
             assert immediate <= allowed, f"{f}: {name}: {immediate} of {loads} loads are waited on immediately"
+
+
+def test_memo_is_a_bounded_lru():
+    """graph_runner.Memo, the one host-side memo of both detector classes: a hit refreshes recency, a miss stores make() and evicts the
+    OLDEST entry beyond the capacity (not everything), make() runs once per live key, memoise=True registers the stored tensors."""
+    from mq_det_amd.modeling.graph_runner import Memo, is_memoised
+    made = []
+
+    def make(k):
+        return lambda: made.append(k) or (torch.full((2,), float(len(made))), k)
+    m = Memo(3, memoise=True)
+    a = m.get("a", make("a"))
+    m.get("b", make("b"))
+    m.get("c", make("c"))
+    assert m.get("a", make("a")) is a and made == ["a", "b", "c"] and len(m) == 3     # a hit: no make(), a is now the newest
+    m.get("d", make("d"))                                                             # evicts b, the oldest
+    assert len(m) == 3 and "b" not in m and all(k in m for k in "acd")
+    assert m.get("a", make("a")) is a and m.get("c", make("c"))[1] == "c" and made == ["a", "b", "c", "d"]
+    m.get("b", make("b"))                                                             # b again: made again, evicts d (a and c were just read)
+    assert made == ["a", "b", "c", "d", "b"] and "d" not in m and len(m) == 3
+    assert is_memoised(a[0]) and is_memoised(m.get("b", make("b"))[0])
+    plain = Memo(2)
+    t = plain.get("k", lambda: torch.zeros(2))
+    assert plain.get("k", lambda: torch.ones(2)) is t and not is_memoised(t)
+    m.clear()
+    assert len(m) == 0 and "a" not in m
+
+
+# positive_map, max_kv, onehot -> cleaned map, labels_in_caption, pm_key, scoring map, scoring labels, max_kv; all with T = 32.  Written down from the
+# rule (prepare_positive_map's docstring); the rows without ONEHOT and without a bare int are also what the forward() of the commit before computed.
+_PM_CASES = [
+    ({1: 3, 2: [4, 5]}, 8, False, {1: [3], 2: [4, 5]}, [1, 2], ((1, (3,)), (2, (4, 5))), None, None, 8),                    # an int entry
+    ({1: [2], 2: []}, 6, False, {1: [2], 2: []}, [1], ((1, (2,)),), None, None, 6),                                        # an empty label
+    ({1: [31], 2: [40]}, 20, False, {1: [31], 2: []}, [1], ((1, (31,)),), None, None, 32),                                 # 40 >= T: dropped
+    ({1: [9]}, 0, False, {1: [9]}, [1], ((1, (9,)),), None, None, 0),                                                      # bound unknown
+    ({1: [2, 9], 2: [4]}, 5, False, {1: [2, 9], 2: [4]}, [1, 2], ((1, (2, 9)), (2, (4,))), None, None, 10),                # widened to token 9
+    ({k: [2 * k] for k in range(1, 13)}, 5, True, {k: [2 * k] for k in range(1, 13)}, list(range(1, 13)),
+     tuple((k, (2 * k,)) for k in range(1, 13)), {j + 1: [j] for j in range(12)}, list(range(1, 13)), 12),                 # ONEHOT: 12 columns
+    ({k: [k % 30] for k in range(1, 41)}, 5, True, {k: [k % 30] for k in range(1, 41)}, list(range(1, 41)),
+     tuple((k, (k % 30,)) for k in range(1, 41)), {j + 1: [j] for j in range(32)}, list(range(1, 33)), 32),                # ONEHOT: clamped to T
+    ({1: [30], 2: [3]}, 5, True, {1: [30], 2: [3]}, [1, 2], ((1, (30,)), (2, (3,))), {1: [0], 2: [1]}, [1, 2], 5),          # ONEHOT: tokens are not scored
+]
+
+
+@pytest.mark.parametrize("case", range(len(_PM_CASES)))
+def test_prepare_positive_map(case):
+    from mq_det_amd.modeling.query_selector import prepare_positive_map
+    pm, kv, onehot, want_pm, want_labels, want_key, want_smap, want_slabels, want_kv = _PM_CASES[case]
+    got = prepare_positive_map(pm, 32, kv, onehot)
+    if want_smap is None:                                   # not ONEHOT: the cleaned map itself is scored
+        want_smap, want_slabels = want_pm, want_labels
+    assert got == (want_pm, want_labels, want_key, want_smap, want_slabels, want_kv)
+    assert all(isinstance(v, list) for v in got[0].values()) and hash(got[2]) is not None
+
+
+def test_cached_features_identity_and_version(monkeypatch):
+    """DeviceModel._cached_features through GeneralizedVLRCNN_New._features (emulated ops, tiny spec): the same pixel tensor again is a hit, an in-place
+    write (version counter) a miss, reuse False recomputes, and with backbone_cache off nothing is stored or counted."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import ops_emulation as emu
+    import parity_checks as pc
+    from oracle import tiny_spec
+    from mq_det_amd import get_cfg, ops
+    from mq_det_amd.modeling import detector, pipeline
+    from mq_det_amd.structures import ImageList
+    spec = tiny_spec()
+    cfg = get_cfg()
+    cfg.MODEL.SWINT.DEPTHS, cfg.MODEL.DYHEAD.NUM_CONVS, cfg.MODEL.DYHEAD.NUM_CLASSES = spec.swin_depths, spec.dyhead_convs, spec.num_classes
+    LB = cfg.MODEL.LANGUAGE_BACKBONE
+    LB.NUM_HIDDEN_LAYERS, LB.QV_START, LB.BERT_VOCAB_SIZE = spec.bert_layers, spec.qv_start, spec.vocab
+    cfg.MODEL.DYHEAD.LEVEL_STREAMS = False
+    emu.patch_into(monkeypatch, ops)
+
+    def prepare(self, device=None):
+        self._plan = pipeline.build_plan(self.state_dict(), self.cfg, torch.device("cpu"), dtype=torch.float32)
+        self._plan_key, self.use_hip_graph = torch.device("cpu"), False
+        return self._plan
+    monkeypatch.setattr(detector.GeneralizedVLRCNN_New, "prepare", prepare)
+    model = detector.GeneralizedVLRCNN_New(cfg, tokenizer=object())
+    images, sizes, *_ = pc.make_inputs(spec)
+    il = ImageList(images, sizes)
+    st = model.cache_stats
+    feats, pooled = model._features(il)
+    assert (st["backbone_miss"], st["backbone_hit"]) == (1, 0) and pooled is None and len(feats) == 5
+    again, _ = model._features(il)
+    assert (st["backbone_miss"], st["backbone_hit"]) == (1, 1) and all(a is b for a, b in zip(again, feats))
+    images.add_(0)                                          # same values, but the version counter moved: a miss
+    third, _ = model._features(il)
+    assert (st["backbone_miss"], st["backbone_hit"]) == (2, 1) and third[0] is not feats[0] and torch.equal(third[0], feats[0])
+    calls = []
+
+    def make():
+        calls.append(1)
+        return {"feats": third, "pooled": None}
+    rec, hit = model._cached_features(images, False, make)  # reuse_backbone=False: recomputed (and stored) whatever the cache holds
+    assert not hit and calls == [1] and (st["backbone_miss"], st["backbone_hit"]) == (3, 1)
+    rec, hit = model._cached_features(images, None, make)
+    assert hit and calls == [1] and rec["feats"] is third and (st["backbone_miss"], st["backbone_hit"]) == (3, 2)
+    model.backbone_cache = False
+    model._feat_cache = None
+    for _ in range(2):
+        rec, hit = model._cached_features(images, None, make)
+        assert not hit and model._feat_cache is None
+    assert calls == [1, 1, 1] and (st["backbone_miss"], st["backbone_hit"]) == (3, 2)
