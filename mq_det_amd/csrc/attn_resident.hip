@@ -518,6 +518,7 @@ __global__ __launch_bounds__(256) void attn_chunked_combine_kernel(ResAttnParams
 
 template <int D, bool CLAMP>
 static int launch_chunked_c(const ResAttnParams& p, float* ws, int nsplit, hipStream_t stream) {
+  // (ops.attention_chunked_fits in mq_det_amd/ops.py states this size expression against the 160 KB of LDS: change both together)
   constexpr size_t smem = (size_t)2 * (RES_NKMAX * (D + 8) + D * (RES_NKMAX + 8)) * sizeof(half_t) + 4 * RES_NKMAX * sizeof(float);
   static MqOncePerDevice attr_set;
   if (attr_set.first()) {

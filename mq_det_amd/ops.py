@@ -342,6 +342,25 @@ def attention_text(qkv, heads, key_bias=None, clamp=0.0, kv_len=None, max_kv=0, 
     return o
 
 
+LDS_BYTES = 160 * 1024              # LDS of one gfx950 compute unit: the most one workgroup can ask for
+
+
+def attention_chunked_fits(D):
+    """Do the tiles of mq_attn_chunked_fwd fit the LDS at head width D?  The size expression of launch_chunked_c (csrc/attn_resident.hip): two
+    buffers of 256 key rows [256][D + 8] and D value rows [D][256 + 8] in the operand type + 4 x 256 floats.  16-bit operands: 73 KB / 142 KB
+    at D = 32 / 64; precise mode on the device (fp32 tiles): 150 KB at D = 32, 280 KB at D = 64 -- that launch would fail, attention4 sends those
+    shapes to the streaming kernel mq_attn_fwd, whose tiles fit."""
+    elem = 4 if f32_operands() == 1 else 2
+    return 2 * (256 * (D + 8) + D * (256 + 8)) * elem + 4 * 256 * 4 <= LDS_BYTES
+
+
+def align_fused_fits(T, kv_max=0):
+    """Does mq_align_fused_fwd hold the text tile of this caption?  Always with 16-bit operands; precise mode on the device: 264 floats of LDS
+    per live text token, up to 144 of them (16-token blocks) -- the pipeline sends longer captions down the GEMM path."""
+    live = kv_max if 0 < kv_max < T else T
+    return f32_operands() != 1 or -(-live // 16) * 16 <= 144
+
+
 def attention4(q4, k4, vt4, key_bias=None, scale=None, clamp=0.0, nsplit=1, nk=None, kv_len=None, qk_mask=None):
     """General strided form.  q4 [B,Nq,H,D], k4 [B,Nk,H,D], vt4 [B,H,D,Nk_pad] fp16 views with unit last stride
     (a head stride of 0, e.g. from .expand(), shares the operand across heads); key_bias None, [B,Nk] or [B,H,Nk]
@@ -387,7 +406,7 @@ def attention4(q4, k4, vt4, key_bias=None, scale=None, clamp=0.0, nsplit=1, nk=N
     ws = None
     if nsplit > 1:
         ws = torch.empty(lib.mq_attn_workspace_bytes(B, H, Nq, D, nsplit) // 4, dtype=torch.float32, device=q4.device)
-    if qk_mask is None and D in (32, 64) and o.stride(1) % 4 == 0 and KERNELS["ATTN_RESIDENT"] == 1:
+    if qk_mask is None and D in (32, 64) and o.stride(1) % 4 == 0 and KERNELS["ATTN_RESIDENT"] == 1 and attention_chunked_fits(D):
         # long key sequences / key splits on the chunked S^T kernel (csrc/attn_resident.hip)
         with _timed(f"attn_chk_d{D}_nq{Nq}_nk{Nk}_s{nsplit}"):
             rc = _fn(lib, "mq_attn_chunked_fwd", q4)(
@@ -1290,9 +1309,8 @@ def align_fused(tok, tk, tbias, wbc, bbc, scales, tokidx, sizes, thr, agg=0, kv_
     assert tbias.dtype == torch.float32 and tbias.shape == (B, T) and tbias.is_contiguous()
     assert bbc.dtype == scales.dtype == torch.float32 and bbc.numel() >= 8 and scales.numel() >= NL
     assert tokidx.dtype == torch.int32 and tokidx.is_contiguous() and (tokidx.dim() == 2 or tokidx.shape[0] == B)
-    live = kv_max if 0 < kv_max < T else T
-    if f32_operands() == 1 and -(-live // 16) * 16 > 144:
-        raise RuntimeError(f"mq_align_fused_fwd_f32: the text tile of {live} live tokens does not fit the LDS at fp32 (up to 144; the GEMM path takes longer captions)")
+    if not align_fused_fits(T, kv_max):
+        raise RuntimeError(f"mq_align_fused_fwd_f32: the text tile of {kv_max if 0 < kv_max < T else T} live tokens does not fit the LDS at fp32 (up to 144; the GEMM path takes longer captions)")
     dev = tok.device
     ranked = torch.empty(B * N * L, dtype=torch.float32, device=dev)
     cls = torch.empty(B * N * L, dtype=torch.float32, device=dev) if want_cls else None
