@@ -128,7 +128,7 @@ def get_cfg():
         ENABLED=True, QUERY_BANK_PATH="", NUM_QUERY_PER_CLASS=5, VISION_SCALE=1.0, SHARE_KV=False,
         SELECT_FPN_LEVEL=True, PURE_TEXT_RATE=0.0, TEXT_DROPOUT=0.0, CONDITION_GATE=True, NONLINEAR_GATE=True,
         NO_CAT=True, FIX_ATTN_GATE=-1.0, ADD_ADAPT_LAYER=False, QUERY_FUSION=False, DISABLE_SELECTOR=False,
-        LEARNABLE_BANK=False, ADD_VISION_LAYER=False, RANDOM_KSHOT=False, MASK_DURING_INFERENCE=False,
+        LEARNABLE_BANK=False, ADD_VISION_LAYER=False, RANDOM_KSHOT=False, MASK_DURING_INFERENCE=False, NEW_MASK_TOKEN=False,
         AUGMENT_IMAGE_WITH_QUERY=False, RETURN_ATTN_GATE_VALUE=False, EXPAND_RATIO=1.5, MAX_QUERY_NUMBER=5000,
         SIMILARITY_THRESHOLD=0.85,
         # the bank-building and test-time online-update loops (mq_det_amd.query_bank; defaults.py:903-935)

@@ -6,6 +6,9 @@ positive_map=None, greenlight_map=None, return_backbone_features=False)` -> `lis
 (`backbone.body/.fpn`, `language_backbone`, `rpn.head`, `query_selector`, `tokenizer`) and the same
 `state_dict()` keys, so `tools/test_grounding_net.py` / `engine/inference.py` / `GLIPDemo` can drive it
 unchanged.  Inference only: training mode raises NotImplementedError.
+The README's three evaluation modes are settings of this forward and need nothing from its callers: text + vision queries (default),
+text only (`VISION_QUERY.ENABLED False`), vision only (`VISION_QUERY.MASK_DURING_INFERENCE True VISION_QUERY.TEXT_DROPOUT 1.0`,
+:397-407 -> `_masked_ids`).
 Differences by design: fp16 compute on MI355X HIP kernels; B > 1 is allowed with vision queries (the
 reference asserts B == 1, :354); post-processing has a single device->host sync per forward.
 """
@@ -20,7 +23,8 @@ from . import pipeline
 from .device_model import DeviceModel, compute_dtype  # noqa: F401  (compute_dtype: re-exported)
 from .graph_runner import Memo
 from .params import Container, build_param_tree
-from .query_selector import build_token_index, prepare_positive_map
+from .query_selector import (build_token_index, consume_text_dropout_draws, prepare_positive_map, text_dropout_mask,
+                             text_dropout_rate)
 
 
 def expand_bbox(box_list, expand_ratio=1.5):
@@ -84,6 +88,7 @@ class GeneralizedVLRCNN_New(DeviceModel):
         # host memos of a caption / an image-size list; their tensors are registered with memoised(): a graph replay skips copying them
         self._tok_cache, self._tokidx_cache, self._wh_cache, self._live_cache = (Memo(256, memoise=True) for _ in range(4))
         self._front_cache = Memo(cfg.MODEL.get("LANG_FRONT_CACHE", 64))   # image-independent BERT layers per caption (f1)
+        self._mask_cache = Memo(256, memoise=True)                # token ids with the [MASK]ed category words (_masked_ids)
         # lanes of the staggered schedule (_staggered_program); 1 = the whole batch as one lane.  MQ_MICRO_BATCHES overrides (A/B runs)
         self.micro_batches = int(os.environ.get("MQ_MICRO_BATCHES", cfg.MODEL.get("MICRO_BATCHES", 1)))
         self.cache_stats.update(front_hit=0, front_miss=0)
@@ -127,6 +132,7 @@ class GeneralizedVLRCNN_New(DeviceModel):
         if cfg.VISION_QUERY.get("ADD_ADAPT_LAYER", False) or cfg.VISION_QUERY.get("QUERY_FUSION", False) or \
                 cfg.VISION_QUERY.get("AUGMENT_IMAGE_WITH_QUERY", False):
             raise NotImplementedError("VISION_QUERY.ADD_ADAPT_LAYER / QUERY_FUSION / AUGMENT_IMAGE_WITH_QUERY are not implemented")
+        text_dropout_rate(cfg)                                    # VISION_QUERY.MASK_DURING_INFERENCE with PURE_TEXT_RATE != 0
 
     # ------------------------------------------------------------------ reference API
     @torch.no_grad()
@@ -168,6 +174,44 @@ class GeneralizedVLRCNN_New(DeviceModel):
             return tok["input_ids"].to(device), am.to(device), max_kv
         return self._tok_cache.get((tuple(captions), str(device)), make)
 
+    def _masked_ids(self, input_ids, cap_key, pm_key, labels, positive_map, dev, n_images=None):
+        """Vision-only evaluation (VISION_QUERY.MASK_DURING_INFERENCE + TEXT_DROPOUT, generalized_vl_rcnn_new.py:397-407): the tokenizer's ids
+        with the words of every label that has vision queries replaced by [MASK] -> (input_ids, cap_key, mkey).  Nothing else changes:
+        attention mask, positive map, scoring maps and the vision-query index are those of the unmasked caption.
+        `mkey` is the MASK SIGNATURE every memo of a caption carries beside the caption itself (the live-row slice, the front cache, the
+        fronts of forward_chunks): None when nothing is masked -- mode off, no bank, no label of this caption in the bank --, else the
+        cleaned positive map + the labels the bank has rows for.  It is recomputed from the bank on every call (a dict lookup per label,
+        what `QuerySelector.deterministic` already does), so a bank that gained or lost labels changes it without `clear_caches()`.
+        TEXT_DROPOUT >= 1 (the README's setting): the masked ids are a function of (caption, mkey) and memoised -- a hit costs no device
+        work, and the SAME tensor object comes back, which is what lets a HIP-graph replay skip copying it.
+        0 < TEXT_DROPOUT < 1: one draw of Python's global generator per (image, label) like the reference, and nothing about this call is
+        memoised (`cap_key` comes back None: the forward then treats the ids like caller-supplied ones).
+        `n_images` (forward_chunks: one id row per chunk serves every image): the images VISION_QUERY.REFERENCE_RNG_STREAM draws for."""
+        p = text_dropout_rate(self.cfg)
+        if p <= 0.0 or cap_key is None or not self._use_vq():
+            return input_ids, cap_key, None
+        sel = self.query_selector
+        mask_id = getattr(self.tokenizer, "mask_token_id", None)
+        if mask_id is None:
+            raise RuntimeError("VISION_QUERY.MASK_DURING_INFERENCE: the tokenizer has no [MASK] token (mask_token_id is None)")
+        B, T = input_ids.shape
+        if p < 1.0:
+            mask = text_dropout_mask(labels, positive_map, sel.has_vision_query, T, p, B)
+            if mask is None:
+                return input_ids, cap_key, None
+            return input_ids.masked_fill(mask.to(dev), mask_id), None, None
+        if sel.reference_rng:
+            consume_text_dropout_draws(B if n_images is None else n_images, len(labels))
+        masked = tuple(lab for lab in labels if sel.has_vision_query(lab))
+        if not masked:
+            return input_ids, cap_key, None
+        mkey = (pm_key, masked)
+
+        def make():
+            mask = text_dropout_mask(masked, positive_map, lambda lab: True, T, 1.0, B)
+            return input_ids.masked_fill(mask.to(dev), mask_id)
+        return self._mask_cache.get((cap_key, mkey, str(dev)), make), cap_key, mkey
+
     def _live_len(self, T, max_kv):
         """Text positions the device programs run on: 16 ceil(max_kv / 16) (the key-block granularity of the attention kernels; VLFuse takes
         T % 8 == 0), or all T when the bound is unknown or MODEL.LANGUAGE_BACKBONE.COMPACT_TEXT is off."""
@@ -179,12 +223,12 @@ class GeneralizedVLRCNN_New(DeviceModel):
             return T
         return min(T, -(-int(max_kv) // 16) * 16)
 
-    def _live_slice(self, input_ids, attention_mask, Tl, cap_key, dev):
-        """input_ids / attention_mask cut to their first Tl columns as contiguous tensors (memoised per caption: the HIP-graph replay copies
-        its inputs into static buffers, the same two tensors serve every call of a caption)."""
+    def _live_slice(self, input_ids, attention_mask, Tl, cap_key, dev, mkey=None):
+        """input_ids / attention_mask cut to their first Tl columns as contiguous tensors (memoised per caption and mask signature: the
+        HIP-graph replay copies its inputs into static buffers, the same two tensors serve every call of a caption)."""
         def make():
             return input_ids[:, :Tl].contiguous(), attention_mask[:, :Tl].contiguous()
-        return make() if cap_key is None else self._live_cache.get((cap_key, Tl, str(dev)), make)
+        return make() if cap_key is None else self._live_cache.get((cap_key, Tl, str(dev), mkey), make)
 
     def _im_wh(self, images, dev):
         """[B, 2] fp32 (width, height) of every image, memoised per size list."""
@@ -409,9 +453,10 @@ class GeneralizedVLRCNN_New(DeviceModel):
         # the MAX_QUERY_LEN = 256 the caption is padded to.  Padded positions are masked KEYS everywhere (BERT, GCP, VLFuse) and are never
         # scored, so no live output depends on them -- but as ROWS they went through every text-side GEMM, LayerNorm and elementwise kernel
         # (141-token caption: 44 % of those rows).  The key-length bucket is part of the HIP-graph key already, so Tl adds no graph.
+        input_ids, cap_key, mkey = self._masked_ids(input_ids, cap_key, pm_key, labels_in_caption, positive_map, dev)
         Tl = self._live_len(T, max_kv)
         if Tl < T:
-            input_ids, attention_mask = self._live_slice(input_ids, attention_mask, Tl, cap_key, dev)
+            input_ids, attention_mask = self._live_slice(input_ids, attention_mask, Tl, cap_key, dev, mkey)
         vision = idx = None
         if self._use_vq():
             vision, idx = self.query_selector.select_cached(pm_key, labels_in_caption, positive_map, Bn, Tl, dev, dtype)
@@ -430,7 +475,7 @@ class GeneralizedVLRCNN_New(DeviceModel):
         # f1: the pixels of the previous call (same tensor object, not modified since) -> cached Swin / FPN features;
         # a caption seen before -> cached image-independent BERT layers
         src = images.tensors
-        fkey = (cap_key, Bn, vision is not None, Tl)
+        fkey = (cap_key, Bn, vision is not None, Tl, mkey)
         out = None
 
         def full():                                               # miss: the whole device forward; the caches keep CLONES of its features
@@ -504,12 +549,13 @@ class GeneralizedVLRCNN_New(DeviceModel):
         self.cache_stats["front_hit" if key is not None and key in self._front_cache else "front_miss"] += 1
         return make() if key is None else self._front_cache.get(key, make)
 
-    def _front_for(self, caption, dev, use_vq):
-        """Image-independent BERT layers of ONE caption (batch 1), cached per caption."""
+    def _front_for(self, caption, dev, use_vq, masked_ids=None, mkey=None):
+        """Image-independent BERT layers of ONE caption (batch 1), cached per caption and mask signature (`masked_ids`: the caption's ids
+        with the [MASK]ed words of `mkey`, _masked_ids)."""
         def make():
             ids, am, kv = self.tokenize([caption], dev)
-            return pipeline.language_front(self._plan, self.cfg, ids, am, use_vq, max_kv=kv)
-        return self._front(((caption,), 1, use_vq), make)
+            return pipeline.language_front(self._plan, self.cfg, ids if mkey is None else masked_ids, am, use_vq, max_kv=kv)
+        return self._front(((caption,), 1, use_vq, mkey), make)
 
     @torch.no_grad()
     def forward_chunks(self, images, chunks, max_items=32):
@@ -518,10 +564,16 @@ class GeneralizedVLRCNN_New(DeviceModel):
         positive_map=pm) for c, pm in chunks]`, but Swin + FPN run once, the image-independent BERT layers once per caption
         (cached across images), and the image-dependent rest runs with the chunks stacked along the batch dimension
         (up to `max_items` image x chunk items per launch sequence): B = 1 -- the reference's TEST.IMS_PER_BATCH -- no longer
-        means a batch-1 forward.  Returns list (over chunks) of list[BoxList] (over images)."""
+        means a batch-1 forward.  Returns list (over chunks) of list[BoxList] (over images).
+        Vision-only evaluation (_masked_ids) masks every chunk's ids with that chunk's positive map, like the loop above.  With
+        0 < VISION_QUERY.TEXT_DROPOUT < 1 every (chunk, image) item draws its own mask, so no caption-level state can be shared between
+        items: that setting runs the loop above as it is written."""
         if self.training:
             raise NotImplementedError("training forward is out of scope")
         images = to_image_list(images)
+        if self._use_vq() and 0.0 < text_dropout_rate(self.cfg) < 1.0:
+            outs = [self.forward(images, captions=[cap] * images.tensors.shape[0], positive_map=pm) for cap, pm in chunks]
+            return [o[0] if isinstance(o, tuple) else o for o in outs]
         dev = images.tensors.device
         feats, pooled = self._features(images)
         P, cfg = self._plan, self.cfg
@@ -536,10 +588,12 @@ class GeneralizedVLRCNN_New(DeviceModel):
         for g0 in range(0, len(chunks), per):
             grp = chunks[g0:g0 + per]
             g = len(grp)
-            ids, ams, kvs, fronts, pms, labs, smaps = [], [], [], [], [], [], []
+            ids, ams, kvs, fronts, pms, labs, smaps, masked = [], [], [], [], [], [], [], []
             for cap, pm in grp:
                 i, a, kv = self.tokenize([cap], dev)
-                pm, lab, _, smap, slab, kv = prepare_positive_map(pm, i.shape[1], kv, onehot)
+                pm, lab, pm_key, smap, slab, kv = prepare_positive_map(pm, i.shape[1], kv, onehot)
+                i, _, mkey = self._masked_ids(i, (cap,), pm_key, lab, pm, dev, n_images=Bn)
+                masked.append((i, mkey))                          # all MAX_QUERY_LEN positions: what the cached front is computed from
                 ids.append(i)
                 ams.append(a)
                 kvs.append(kv)
@@ -555,8 +609,8 @@ class GeneralizedVLRCNN_New(DeviceModel):
                                                          T, dev, dtype)
                 if vision.shape[1] == 0:
                     vision = idx = None
-            for cap, _ in grp:
-                fronts.append(self._front_for(cap, dev, vision is not None))
+            for (cap, _), (i, mkey) in zip(grp, masked):
+                fronts.append(self._front_for(cap, dev, vision is not None, i, mkey))
             rep = lambda t: t.repeat_interleave(Bn, 0)            # noqa: E731  [g, ...] -> [g * B, ...] chunk-major
             # (the cached fronts hold all MAX_QUERY_LEN positions of their caption: cut to the group's live length here)
             front = {"x": rep(torch.cat([live(f["x"]) for f in fronts])),

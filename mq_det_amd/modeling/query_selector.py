@@ -8,6 +8,7 @@ EACH of the 6 GCP layers (modeling_bert_new.py:40-63,162-184); it is built once,
 positive_map the caller already holds -- no device work, no sync.
 """
 import os
+import random
 
 import numpy as np
 import torch
@@ -59,6 +60,55 @@ def prepare_positive_map(positive_map, T, max_kv=0, onehot=False):
     return pm, labels, pm_key, score_map, score_labels, max_kv
 
 
+def text_dropout_rate(cfg):
+    """VISION_QUERY.TEXT_DROPOUT when the eval forward masks category words (generalized_vl_rcnn_new.py:397-400), else 0.0: the words of
+    every category that has vision queries become [MASK] before the language backbone -- the README's vision-only evaluation
+    (`VISION_QUERY.MASK_DURING_INFERENCE True VISION_QUERY.TEXT_DROPOUT 1.0`).  Masking runs with ENABLED, TEXT_DROPOUT > 0,
+    MASK_DURING_INFERENCE and NOT NEW_MASK_TOKEN (the learned mask token exists in training only: the reference does nothing with it at
+    inference).  The reference asserts PURE_TEXT_RATE == 0 then (:399); any other value is refused here, by name."""
+    VQ = cfg.VISION_QUERY
+    p = float(VQ.get("TEXT_DROPOUT", 0.0))
+    if not (VQ.ENABLED and p > 0.0 and VQ.get("MASK_DURING_INFERENCE", False)):
+        return 0.0
+    if VQ.get("PURE_TEXT_RATE", 0.0) != 0.0:
+        raise NotImplementedError(f"VISION_QUERY.PURE_TEXT_RATE = {VQ.PURE_TEXT_RATE}: must be 0 with VISION_QUERY.MASK_DURING_INFERENCE "
+                                  "(the reference asserts it: part text, part vision is not implemented there either)")
+    return 0.0 if VQ.get("NEW_MASK_TOKEN", False) else p
+
+
+def consume_text_dropout_draws(B, n_labels):
+    """The draws of `text_dropout_mask` without the mask: one `random.random()` per (image, label)."""
+    for _ in range(B * n_labels):
+        random.random()
+
+
+def text_dropout_mask(labels, positive_map, has_query, T, p, B, reference_rng=False):
+    """[B, T] bool, True where `input_ids` become the tokenizer's [MASK] id (generalized_vl_rcnn_new.py:401-407, eval), or None when no
+    position is masked.  For every image i and, within it, every label j of `labels` (the caption's labels in positive-map order) one
+    `random.random()` of Python's global generator is drawn FIRST -- also for labels without vision queries --; label j is masked in image i
+    when the draw is < p AND `has_query(label)`: all of `positive_map[label]`.
+    p >= 1: every draw succeeds, so the mask is a function of the bank alone and the same for every image; the draws are then skipped
+    unless `reference_rng` (VISION_QUERY.REFERENCE_RNG_STREAM: consume the generator exactly like the reference, QuerySelector.__init__).
+    Host only: the caller moves the mask to the device."""
+    has = [bool(has_query(lab)) for lab in labels]
+    if p >= 1.0:
+        if reference_rng:
+            consume_text_dropout_draws(B, len(labels))
+        hit = [has] * B
+    else:
+        hit = [[(random.random() < p) and h for h in has] for _ in range(B)]       # the draw comes first: `and` must not skip it
+    if not any(any(row) for row in hit):
+        return None
+    mask = torch.zeros(B, T, dtype=torch.bool)
+    for i, row in enumerate(hit if p < 1.0 else hit[:1]):
+        for lab, h in zip(labels, row):
+            if h:
+                mask[i, list(positive_map[lab])] = True
+    if p >= 1.0:
+        mask[1:] = mask[0]
+    return mask
+
+
 class QuerySelector(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -94,6 +144,10 @@ class QuerySelector(nn.Module):
         if cand is None or isinstance(cand, (list, tuple)) or len(cand) == 0:
             return None
         return cand
+
+    def has_vision_query(self, label):
+        """The reference's `has_vision_query` flag of a label (query_selector.py:77-78): the bank holds at least one row for it."""
+        return self._candidates(label) is not None
 
     def deterministic(self, labels):
         """True when no label of `labels` holds more bank rows than NUM_QUERY_PER_CLASS: the reference's eval-mode draw

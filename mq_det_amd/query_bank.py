@@ -236,6 +236,8 @@ def online_update(model, data_loader, device="cuda", cfg=None, num_turns=1, save
     `queries_and_maps` = `(all_queries, all_positive_map_label_to_token)` of the caller's `create_queries_and_maps_from_dataset` (the data
     layer is not part of this package).  Only TEST.EVAL_TASK = "detection"; TEST.USE_MULTISCALE raises NotImplementedError, as in the
     reference.  The bank starts from VISION_QUERY.QUERY_BANK_PATH when that file exists, else empty.
+    The detections come from `model(...)`: with VISION_QUERY.MASK_DURING_INFERENCE (vision-only evaluation, detector._masked_ids) the words of
+    the labels the model's bank has rows for are masked, and `model.load_query_bank` between turns changes that set with the bank.
 
     Two deliberate differences from the reference:
       * batches of more than one image are accepted (the reference asserts 1, "TODO: support batched outputs").  The bank only enters the

@@ -223,7 +223,9 @@ def check_supported(model):
 
 @torch.no_grad()
 def im_detect_bbox_aug(model, images, device, captions=None, positive_map_label_to_token=None):
-    """box_aug.py:12-63 (SPECIAL_NMS 'none'), reading model.cfg.  images: RGB PIL images (BBoxAugCollator) or HWC uint8 tensors / arrays."""
+    """box_aug.py:12-63 (SPECIAL_NMS 'none'), reading model.cfg.  images: RGB PIL images (BBoxAugCollator) or HWC uint8 tensors / arrays.
+    Every transform goes through `model(...)`, so vision-only evaluation (VISION_QUERY.MASK_DURING_INFERENCE, detector._masked_ids) applies
+    to each of them with no code here."""
     check_supported(model)
     cfg = model.cfg
     device = torch.device(device)
