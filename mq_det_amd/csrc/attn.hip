@@ -370,17 +370,9 @@ template <int D, int RB, bool MASK>
 static int launch_attn(const AttnParams& p, hipStream_t stream) {
   constexpr int BM = 4 * RB * 16, BN = 64;
   constexpr size_t smem = (size_t)(BN * (D + 8) + D * (BN + 8) + 4 * RB * 16 * (BN + 8) + (D >= 256 ? BM * (D + 8) : 0)) * sizeof(half_t) + BN * sizeof(float);
-  static MqOncePerDevice attr_set;
-  if (attr_set.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_kernel<D, RB, MASK>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done();
-  }
   const int groups = p.B * p.nsplit, members = p.H * ((p.Nq + BM - 1) / BM);
   dim3 grid((unsigned)(8 * ((groups + 7) / 8) * members));
-  hipLaunchKernelGGL((attn_fwd_kernel<D, RB, MASK>), grid, dim3(256), smem, stream, p);
-  MQ_CHECK_LAUNCH();
+  if (int rc = mq_launch<attn_fwd_kernel<D, RB, MASK>>(grid, dim3(256), smem, stream, p)) return rc;
   if (p.nsplit > 1) {
     long total = (long)p.B * p.H * p.Nq;
     hipLaunchKernelGGL((attn_combine_kernel<D>), dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, p);

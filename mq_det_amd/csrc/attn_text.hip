@@ -203,17 +203,8 @@ static int launch_text(const TextAttnParams& p, hipStream_t stream) {
   constexpr int KS = D + 16;
   const int cap = p.nblk_cap, cap_st = (cap + 1) / 2;
   const size_t smem = (size_t)(16 * cap + 32 * cap_st) * KS * sizeof(half_t) + (size_t)2 * 32 * cap_st * sizeof(float);
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    constexpr size_t smax = (size_t)(16 * NBM + 32 * ((NBM + 1) / 2)) * KS * sizeof(half_t) + (size_t)2 * 32 * ((NBM + 1) / 2) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void*)attn_text_kernel<D, NBM, CLAMP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smax);
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
   const int qtiles = (p.Nq + TXT_BM - 1) / TXT_BM;
-  hipLaunchKernelGGL((attn_text_kernel<D, NBM, CLAMP>), dim3((unsigned)(qtiles * p.B * p.H)), dim3(256), smem, stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<attn_text_kernel<D, NBM, CLAMP>>(dim3((unsigned)(qtiles * p.B * p.H)), dim3(256), smem, stream, p);
 }
 
 // q [B, Nq, H, D], k / v [B, Nk, H, D] 16-bit views with unit last stride (row stride *_rs, head stride *_hs, batch stride *_bs in

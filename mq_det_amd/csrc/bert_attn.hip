@@ -25,15 +25,6 @@ constexpr int BA_BK = 64, BA_XP = BA_BK + 16;      // k-chunk of the projection;
 constexpr int BA_C = 768;                          // hidden width (BERT-base; compile time: the chunk loop is unrolled completely)
 constexpr float BA_LOG2E = 1.4426950408889634f;
 
-template <int I, int N, class F>
-__device__ __forceinline__ void ba_static_for_impl(F& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ba_static_for_impl<I + 1, N>(f);
-  }
-}
-template <int N, class F>
-__device__ __forceinline__ void ba_static_for(F f) { ba_static_for_impl<0, N>(f); }
 }  // namespace
 
 struct BertAttnParams {
@@ -154,7 +145,7 @@ __global__ __launch_bounds__(512, 2) void bert_attn_qkv_kernel(BertAttnParams p)
   load_w(wf[1], 1);
   store_x(xr[0], 0);
   __syncthreads();
-  ba_static_for<NSTEPS>([&](auto kc) __attribute__((always_inline)) {
+  mq_static_for<NSTEPS>([&](auto kc) __attribute__((always_inline)) {
     constexpr int k = decltype(kc)::value;
     if constexpr (k + 2 < NSTEPS) {
       load_x(xr[k & 1], k + 2);                      // (xr[k & 1] held chunk k: stored in chunk k - 1)
@@ -265,15 +256,7 @@ static int launch_bert_attn(const BertAttnParams& p, hipStream_t stream) {
     const size_t rows = 32 * (size_t)((cap + 1) >> 1);
     return 3 * rows * BA_KS * sizeof(half_t) + 2 * rows * sizeof(float);
   };
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)bert_attn_qkv_kernel<NBM, CLAMP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes(NBM));
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
-  hipLaunchKernelGGL((bert_attn_qkv_kernel<NBM, CLAMP>), dim3((unsigned)(p.B * p.H)), dim3(512), bytes(p.nblk_cap), stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<bert_attn_qkv_kernel<NBM, CLAMP>>(dim3((unsigned)(p.B * p.H)), dim3(512), bytes(p.nblk_cap), stream, p);
 }
 
 // x [B, T, C] operand type (row stride x_rs, batch stride x_bs, elements; % 8), w [3 C, C] = the layer's q | k | v projection weight in MFMA

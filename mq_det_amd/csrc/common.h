@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <type_traits>
 
 // Element type of the 16-bit operands.  Every kernel source is compiled TWICE (mq_det_amd/build.py): as is -- half_t = fp16, the
 // entry points of include/mqdet_hip.h -- and with -DMQ_BF16 -- half_t = bf16 (v_mfma_f32_16x16x32_bf16), entry points with the
@@ -57,7 +59,14 @@ typedef float float2_ __attribute__((ext_vector_type(2)));
 
 #define MQ_NEG_BIG (-1.0e30f)
 
+// 1: the split-precise build -- fp32 operands carried through the fp16 matrix cores as (hi, lo) pairs (below); 0: the 16-bit builds (and -DMQ_F32_EXACT)
 #if defined(MQ_F32) && !defined(MQ_F32_EXACT)
+#define MQ_SPLIT_OPERANDS 1
+#else
+#define MQ_SPLIT_OPERANDS 0
+#endif
+
+#if MQ_SPLIT_OPERANDS
 // The SPLIT-PRECISE contraction (round 6; VERDICT r5 #1b).  An fp32 operand x is carried through the fp16 matrix cores as x = hi + lo / 2^11:
 //   hi = fp16(x)                      (11 significant bits, round to nearest even)
 //   lo = fp16((x - hi) * 2^11)        (x - hi is exact in fp32; the power-of-two pre-scale keeps lo a NORMAL fp16 number wherever hi is one)
@@ -104,7 +113,7 @@ __device__ __forceinline__ void mq_split4(mq_f32x4 x, mq_h16x4& hi, mq_h16x4& lo
 #endif
 
 __device__ __forceinline__ float4_ mfma16(half8 a, half8 b, float4_ c) {
-#if defined(MQ_F32) && !defined(MQ_F32_EXACT)
+#if MQ_SPLIT_OPERANDS
 #if defined(MQ_SIMT_EMULATION)
   return simt_mfma_16x16x32_split(a, b, c);         // tests/simt: the same split and the same three products, one lane exchange instead of three
 #else
@@ -126,6 +135,29 @@ __device__ __forceinline__ float4_ mfma16(half8 a, half8 b, float4_ c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 #endif
 }
+
+// An MFMA operand fragment as the kernels keep it when it feeds SEVERAL MFMAs: the split-precise build splits it once (mq_to_frag) into (hi, lo)
+// and contracts the pairs; in the other builds it is the half8 itself.
+#if MQ_SPLIT_OPERANDS
+typedef mq_split8 mq_frag;
+__device__ __forceinline__ mq_frag mq_to_frag(half8 x) { return mq_split(x); }
+__device__ __forceinline__ float4_ mq_frag_mfma(const mq_frag& a, const mq_frag& b, float4_ c) { return mfma16_split(a, b, c); }
+#else
+typedef half8 mq_frag;
+__device__ __forceinline__ mq_frag mq_to_frag(half8 x) { return x; }
+__device__ __forceinline__ float4_ mq_frag_mfma(mq_frag a, mq_frag b, float4_ c) { return mfma16(a, b, c); }
+#endif
+
+// compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
+template <int I, int N, class F>
+__device__ __forceinline__ void mq_static_for_impl(F& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    mq_static_for_impl<I + 1, N>(f);
+  }
+}
+template <int N, class F>
+__device__ __forceinline__ void mq_static_for(F f) { mq_static_for_impl<0, N>(f); }
 
 __device__ __forceinline__ half8 zero8() {
   half8 z;
@@ -233,41 +265,16 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// hipFuncSetAttribute (LDS above 64 KB) and the CU count are per-DEVICE properties: a process that drives several GPUs sets / reads them
-// once per device, not once per process.
-// (the device index found by first() / need() reaches done() through a THREAD-LOCAL, not through a member of the shared static
-// object -- two host threads driving different GPUs cannot mark each other's device.)
-static thread_local int mq_tl_dev = -1;
-struct MqOncePerDevice {
-  volatile bool set_[32] = {};
-  bool first() {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) { mq_tl_dev = -1; return true; }
-    mq_tl_dev = dev;
-    return !set_[dev];
-  }
-  void done() { if (mq_tl_dev >= 0) set_[mq_tl_dev] = true; }
-};
-// the same for launchers whose dynamic LDS size depends on the call: the largest size the attribute was set to, per device
-struct MqMaxPerDevice {
-  volatile size_t max_[32] = {};
-  bool need(size_t bytes) {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) { mq_tl_dev = -1; return true; }
-    mq_tl_dev = dev;
-    return bytes > max_[dev];
-  }
-  void done(size_t bytes) { if (mq_tl_dev >= 0 && bytes > max_[mq_tl_dev]) max_[mq_tl_dev] = bytes; }
-};
+// The CU count is a per-DEVICE property: a process that drives several GPUs (one host thread each) reads it once per device.
 static inline int mq_device_cus() {
-  static int cus[32] = {};
+  static std::atomic<int> cus[32] = {};
   int dev = 0, n = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return 256;
-  if (!cus[dev]) {
+  if (!(n = cus[dev].load(std::memory_order_relaxed))) {
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
+    cus[dev].store(n, std::memory_order_relaxed);
   }
-  return cus[dev];
+  return n;
 }
 
 #define MQ_CHECK_LAUNCH()                                   \
@@ -275,3 +282,23 @@ static inline int mq_device_cus() {
     hipError_t e__ = hipGetLastError();                     \
     if (e__ != hipSuccess) return (int)e__;                 \
   } while (0)
+
+// Every launch with dynamic LDS: raise the kernel's limit (hipFuncSetAttribute, needed above 64 KB) where this device has not seen that
+// many bytes for THIS kernel yet, launch, return the launch's error code.  The largest size set so far is kept per device in a static of
+// the function template -- one per kernel instantiation, nothing to list.  A failed attribute call is returned without a launch and without
+// a mark (the next call tries again); with an unknown device index the attribute is set on every call.
+template <auto Kernel, class... A>
+static int mq_launch(dim3 grid, dim3 block, size_t smem, hipStream_t stream, const A&... args) {
+  if (smem) {
+    static std::atomic<size_t> max_[32] = {};
+    int dev = -1;
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32;
+    if (!known || smem > max_[dev].load(std::memory_order_relaxed)) {
+      hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e != hipSuccess) return (int)e;
+      if (known) max_[dev].store(smem, std::memory_order_relaxed);
+    }
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, smem, stream, args...);
+  return (int)hipGetLastError();
+}

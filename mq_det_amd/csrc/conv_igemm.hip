@@ -213,17 +213,8 @@ static int launch_conv(const ConvParams& p, hipStream_t stream) {
   constexpr size_t tiles = (size_t)(2 * BM * LP + 2 * BN * LP) * sizeof(half_t);
   constexpr size_t ostage = (size_t)BM * (BN + 8) * sizeof(half_t);
   constexpr size_t smem = tiles > ostage ? tiles : ostage;
-  static MqOncePerDevice attr_set;
-  if (attr_set.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_igemm_kernel<DEFORM, BN, WM, WN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done();
-  }
   long M = (long)p.B * p.Ho * p.Wo;
-  hipLaunchKernelGGL((conv_igemm_kernel<DEFORM, BN, WM, WN>), dim3((unsigned)(8 * (((M + BM - 1) / BM + 7) / 8))), dim3(256), smem, stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<conv_igemm_kernel<DEFORM, BN, WM, WN>>(dim3((unsigned)(8 * (((M + BM - 1) / BM + 7) / 8))), dim3(256), smem, stream, p);
 }
 
 static int conv_common(ConvParams& p, const void* x, const void* w, const void* bias, void* out, int B, int H, int W, int C,

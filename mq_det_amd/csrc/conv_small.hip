@@ -152,15 +152,7 @@ extern "C" int MQ_SYM(mq_conv3x3_nchw32_fwd)(const void* x, const void* w, const
   const size_t tiles = (size_t)(CS_WH * CS_WW + 2 * 32) * (CP + 16) * sizeof(half_t);
   const size_t ostage = (size_t)32 * (CS_PH * CS_PW + 4) * sizeof(float);
   const size_t smem = tiles > ostage ? tiles : ostage;
-  static MqMaxPerDevice attr_set;
-  if (attr_set.need(smem)) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done(smem);
-  }
-  hipLaunchKernelGGL(conv3x3_small_kernel, dim3((unsigned)(8 * ((p.tiles_total + 7) / 8))), dim3(256), smem, (hipStream_t)stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<conv3x3_small_kernel>(dim3((unsigned)(8 * ((p.tiles_total + 7) / 8))), dim3(256), smem, (hipStream_t)stream, p);
 }
 
 MQ_NAMESPACE_END

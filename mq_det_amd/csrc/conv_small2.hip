@@ -13,11 +13,6 @@
 // with the fp16 build's pitch, the same bytes as the fp32 tiles -- split ONCE by the thread that stages a chunk; the k-loop reads one 16-byte
 // fragment per plane and issues three fp16 MFMAs (mfma16_split).  (Splitting inside mfma16 cost ~100 VALU instructions per 12 MFMAs here: every
 // fragment feeds only two.)
-#if defined(MQ_F32) && !defined(MQ_F32_EXACT)
-#define MQ_CS_SPLIT 1
-#else
-#define MQ_CS_SPLIT 0
-#endif
 
 MQ_NAMESPACE_BEGIN
 
@@ -70,7 +65,7 @@ __global__ __launch_bounds__(256) void conv3x3_small2_kernel(ConvSmall2Params p)
 #pragma unroll
       for (int i = 0; i < WMAX; ++i) {
         const int c = tid + i * 256;
-#if MQ_CS_SPLIT
+#if MQ_SPLIT_OPERANDS
         if (c < 32 * cpr) {
           const mq_split8 sp = mq_split(wreg[i]);
           _Float16* d = (_Float16*)Ws + (buf * 32 + c / cpr) * XP + (c % cpr) * 8;
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(256) void conv3x3_small2_kernel(ConvSmall2Params p)
         const int px = cc / cpr, ch = cc - px * cpr;
         const int hh = ho0 - 1 + px / CS2_WW, ww = wo0 - 1 + px % CS2_WW;
         const bool inside = hh >= 0 && hh < p.H && ww >= 0 && ww < p.W;
-#if MQ_CS_SPLIT
+#if MQ_SPLIT_OPERANDS
         if (c < total) {
           const mq_split8 sp = mq_split(inside ? v[u] : zero8());
           _Float16* d = (_Float16*)Win + px * XP + ch * 8;
@@ -121,7 +116,7 @@ __global__ __launch_bounds__(256) void conv3x3_small2_kernel(ConvSmall2Params p)
     for (int tap = 0; tap < 9; ++tap) {
       if (tap + 1 < 9) w_issue(tap + 1);
       const int dy = tap / 3, dx = tap - dy * 3;
-#if MQ_CS_SPLIT
+#if MQ_SPLIT_OPERANDS
       const _Float16* a0 = (const _Float16*)Win + ((2 * wave + dy) * CS2_WW + l15 + dx) * XP + lg * 8;
       const _Float16* b0 = (const _Float16*)Ws + ((tap & 1) * 32 + l15) * XP + lg * 8;
       for (int kk = 0; kk < CP / 32; ++kk) {
@@ -197,15 +192,7 @@ extern "C" int MQ_SYM(mq_conv3x3_nchw32_v2_fwd)(const void* x, const void* w, co
   const size_t tiles = (size_t)(CS2_WH * CS2_WW + 2 * 32) * (CP + 16) * sizeof(half_t);
   const size_t ostage = (size_t)32 * (CS2_PH * CS2_PW + 4) * sizeof(float);
   const size_t smem = tiles > ostage ? tiles : ostage;
-  static MqMaxPerDevice attr_set;
-  if (attr_set.need(smem)) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_small2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done(smem);
-  }
-  hipLaunchKernelGGL(conv3x3_small2_kernel, dim3((unsigned)(8 * ((p.tiles_total + 7) / 8))), dim3(256), smem, (hipStream_t)stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<conv3x3_small2_kernel>(dim3((unsigned)(8 * ((p.tiles_total + 7) / 8))), dim3(256), smem, (hipStream_t)stream, p);
 }
 
 // (Round 3 tried a third version without the weight tile: B fragments straight from global memory through a six-step register ring,

@@ -197,15 +197,7 @@ extern "C" int MQ_SYM(mq_conv3x3_nchw32_group_fwd)(const mq_conv_level* levels, 
   constexpr size_t window = (size_t)CS3_WH * CS3_WW * CS3_XP * sizeof(half_t);
   constexpr size_t ostage = (size_t)CS3_NW * 32 * CS3_OP * sizeof(float);
   constexpr size_t smem = window > ostage ? window : ostage;
-  static MqOncePerDevice attr_set;
-  if (attr_set.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done();
-  }
-  hipLaunchKernelGGL(conv3x3_group_kernel, dim3((unsigned)(8 * blocks)), dim3(CS3_NT), smem, (hipStream_t)stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<conv3x3_group_kernel>(dim3((unsigned)(8 * blocks)), dim3(CS3_NT), smem, (hipStream_t)stream, p);
 }
 
 MQ_NAMESPACE_END

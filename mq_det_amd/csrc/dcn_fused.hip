@@ -80,12 +80,7 @@ struct DcnGroup {
 // have a 64-byte pitch: the 16 rows x 4 chunks of a fragment read are 1 KB of consecutive bytes (no swizzle needed).  Tiles stay double-buffered
 // (2 x 48 KB) and the ping-pong of the two wave groups is the one of the 16-bit build.  (Round 5 ran this build with fp32 tiles, ONE buffer,
 // eight v_mfma_f32_16x16x4_f32 per MFMA and 117 spilled VGPRs: 6.4 ms per launch against 0.56 ms with fp16 operands.)
-#if defined(MQ_F32) && !defined(MQ_F32_EXACT)
-#define MQ_DCN_SPLIT 1
-#else
-#define MQ_DCN_SPLIT 0
-#endif
-#if MQ_DCN_SPLIT
+#if MQ_SPLIT_OPERANDS
 typedef mq_f32x4 dcn_gvec;                                   // one 16-byte chunk of operand elements in global memory
 #else
 typedef half8 dcn_gvec;
@@ -102,8 +97,8 @@ typedef half8 dcn_gvec;
 //   * the end-of-step wait as __builtin_amdgcn_s_waitcnt, which the pass books, not as an asm string.
 // dynamic LDS of the kernel without the row table behind it: max(tiles + sampling state, O staging + statistics partials)
 constexpr size_t dcn_smem_main() {
-  constexpr size_t nbuf = (sizeof(half_t) == 4 && !MQ_DCN_SPLIT) ? 1 : 2;
-  constexpr size_t bk = MQ_DCN_SPLIT ? 32 : 64;
+  constexpr size_t nbuf = (sizeof(half_t) == 4 && !MQ_SPLIT_OPERANDS) ? 1 : 2;
+  constexpr size_t bk = MQ_SPLIT_OPERANDS ? 32 : 64;
   constexpr size_t tiles = (size_t)(nbuf * 128 * bk + nbuf * 256 * bk) * sizeof(half_t) + 128 * 9 * sizeof(TapState);
   constexpr size_t ostage = (size_t)128 * (256 + 8) * sizeof(half_t) + (sizeof(half_t) == 4 ? 0 : (size_t)16 * 32 * 24 * sizeof(float));
   return tiles > ostage ? tiles : ostage;
@@ -116,14 +111,14 @@ __device__ __forceinline__ void dcn_scoped_tiles(T* __restrict__ a0, T* __restri
 
 template <int NW, int ABL = 0, int SYNC = 2, bool PLAIN = false, bool FENCE = false, bool BDMA = false>
 __global__ __launch_bounds__(64 * NW) void dcn_igemm8_kernel(DcnGroup g) {
-  constexpr int BM = DCN_PH * DCN_PW, BN = 256, BK = MQ_DCN_SPLIT ? 32 : 64;
+  constexpr int BM = DCN_PH * DCN_PW, BN = 256, BK = MQ_SPLIT_OPERANDS ? 32 : 64;
   constexpr int CH = 16 / (int)sizeof(half_t);               // operand elements per 16-byte chunk (8, or 4 in the split-precise build)
   constexpr int NTH = 64 * NW, RA = 1024 / NTH, JB = 2048 / NTH, IM = 32 / NW;   // threads, A rows / thread, B chunks / thread, row blocks / wave
   static_assert(BM == 128, "tile is 128 positions");
   static_assert(BK * sizeof(half_t) == 128, "a tile row is one 128-byte line per corner");
   // tile buffers: two (ping-pong); only the exact-fp32 build (-DMQ_F32_EXACT: fp32 tiles of 64 channels) has ONE, where every wave runs
   // MFMAs -> barrier -> staging -> barrier
-  constexpr int NBUF = (sizeof(half_t) == 4 && !MQ_DCN_SPLIT) ? 1 : 2;
+  constexpr int NBUF = (sizeof(half_t) == 4 && !MQ_SPLIT_OPERANDS) ? 1 : 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // LDS tiles: rows of 64 halfs = 128 B = 8 chunks of 16 B, NO padding; chunk c of row r is stored at chunk position
   // c ^ (r & 7): conflict-free for the ds_read_b128 fragment reads (16 rows x one chunk) AND for the row-wise
@@ -289,7 +284,7 @@ __global__ __launch_bounds__(64 * NW) void dcn_igemm8_kernel(DcnGroup g) {
   const int ar = tid >> 3, ac = tid & 7;                     // A rows ar + rr * (NTH / 8), rr < RA
   const char* xb = (const char*)(p.x + (long)b * p.x_bs);
   const char* wb = (const char*)p.w;
-#if MQ_DCN_SPLIT
+#if MQ_SPLIT_OPERANDS
   const unsigned a_lds = (unsigned)(ar * BK + ac * CH);                                // fp16 index inside a plane (no swizzle)
 #else
   const unsigned a_lds = (unsigned)(ar * BK + ((ac ^ (ar & 7)) << 3));                 // + 64 * BK for the second row
@@ -299,7 +294,7 @@ __global__ __launch_bounds__(64 * NW) void dcn_igemm8_kernel(DcnGroup g) {
   for (int j = 0; j < JB; ++j) {
     const int c = tid + j * NTH, row = c >> 3, ch = c & 7;
     b_goff[j] = (unsigned)(row * K + ch * CH) * (unsigned)sizeof(half_t);
-#if MQ_DCN_SPLIT
+#if MQ_SPLIT_OPERANDS
     b_lds[j] = (unsigned)(row * BK + ch * CH);
 #else
     b_lds[j] = (unsigned)(row * BK + ((ch ^ (row & 7)) << 3));
@@ -347,7 +342,7 @@ __global__ __launch_bounds__(64 * NW) void dcn_igemm8_kernel(DcnGroup g) {
   // one rounding to fp16) -> its two A-tile rows, and its four weight chunks -> B tile
   auto stage_at = [&](auto SLOT, half_t* a_tile, half_t* b_tile) {      // the two tiles of ONE buffer
     constexpr int s = decltype(SLOT)::value;
-#if MQ_DCN_SPLIT
+#if MQ_SPLIT_OPERANDS
     // planes of the buffer: A hi, A lo, B hi, B lo (fp16); this thread's CH = 4 blended values / weights -> 8 bytes into each plane
     _Float16* a_hi = (_Float16*)a_tile + a_lds;
     _Float16* b_hi = (_Float16*)b_tile;
@@ -435,7 +430,7 @@ __global__ __launch_bounds__(64 * NW) void dcn_igemm8_kernel(DcnGroup g) {
 
   // fragment addressing: row = w? * 64 + i * 16 + l15 (row & 7 == l15 & 7), chunk = kk * 4 + lg
   const unsigned fa = (unsigned)((wr * IM * 16 + l15) * BK), fb = (unsigned)((wc * 64 + l15) * BK);
-#if MQ_DCN_SPLIT
+#if MQ_SPLIT_OPERANDS
   auto mfma_at = [&](const half_t* a_tile, const half_t* b_tile) {   // one 32-deep step: IM x 4 blocks, three fp16 MFMAs each on the planar fragments
     if constexpr (ABL & 8) return;
     const _Float16* At = (const _Float16*)a_tile + fa + lg * 8;
@@ -695,16 +690,32 @@ struct mq_dcn_branch {          // mirrors include/mqdet_hip.h
   int B, H, W, C, oH, oW, N, out_ld, stride, flags;
 };
 
-template <int NW, int SYNC, bool PLAIN, bool BDMA = false>
-static int dcn_launch(dim3 grid, size_t smem, hipStream_t stream, const DcnGroup& g) {
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)dcn_igemm8_kernel<NW, 0, SYNC, PLAIN, false, BDMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
-  hipLaunchKernelGGL((dcn_igemm8_kernel<NW, 0, SYNC, PLAIN, false, BDMA>), grid, dim3(64 * NW), smem, stream, g);
-  return 0;
+// Which instantiation a grouped launch runs -- a pure function of the process-wide switches (nw: MQ_DCN_WAVES, sync: MQ_DCN_SYNC) and of the
+// call (plain: flags bit 1 on every branch AND MQ_DCN_PLAIN; tiled: flags bit 2 on every branch, the weights in LDS-tile order).
+// The 16-bit builds ship 16 waves, the split-precise build 8 (wave tile 64 x 64: the planar hi / lo fragments are twice the registers of the
+// fp16 ones -- 16 waves at 128 VGPRs spill).  Tiled weights: one barrier per k-step by construction, at the waves asked for (split-precise:
+// always 8).  Row-major weights: PLAIN exists with one barrier only; 8 waves of the 16-bit builds only with two, as the general kernel.
+struct DcnPick { int nw, sync; bool plain, bdma; };
+static DcnPick dcn_pick(int nw, int sync, bool plain, bool tiled) {
+  if (tiled) return {MQ_SPLIT_OPERANDS ? 8 : nw, 1, plain, true};
+  if (MQ_SPLIT_OPERANDS && nw == 8) return {8, plain ? 1 : sync, plain, false};
+  if (nw == 16 && sync == 1) return {16, 1, plain, false};
+  return {nw, 2, false, false};
+}
+// ... and the one place that launches it: the instantiations each build has, a pick outside them is -4
+static int dcn_launch(DcnPick k, dim3 grid, size_t smem, hipStream_t stream, const DcnGroup& g) {
+#define MQ_DCN_CASE(NW_, SYNC_, PLAIN_, BDMA_)                                       \
+  if (k.nw == NW_ && k.sync == SYNC_ && k.plain == PLAIN_ && k.bdma == BDMA_)        \
+    return mq_launch<dcn_igemm8_kernel<NW_, 0, SYNC_, PLAIN_, false, BDMA_>>(grid, dim3(64 * NW_), smem, stream, g);
+  MQ_DCN_CASE(8, 1, true, true) MQ_DCN_CASE(8, 1, false, true)
+#if MQ_SPLIT_OPERANDS
+  MQ_DCN_CASE(8, 1, true, false) MQ_DCN_CASE(8, 1, false, false)
+#else
+  MQ_DCN_CASE(16, 1, true, true) MQ_DCN_CASE(16, 1, false, true)
+#endif
+  MQ_DCN_CASE(16, 1, true, false) MQ_DCN_CASE(16, 1, false, false) MQ_DCN_CASE(16, 2, false, false) MQ_DCN_CASE(8, 2, false, false)
+#undef MQ_DCN_CASE
+  return -4;
 }
 
 extern "C" int MQ_SYM(mq_dcnv2_group_fwd)(const mq_dcn_branch* br, int n, void* stream) {
@@ -737,89 +748,30 @@ extern "C" int MQ_SYM(mq_dcnv2_group_fwd)(const mq_dcn_branch* br, int n, void* 
   if (g.n == 0) return 0;
   g.tiles_all = g.first_tile[g.n];
   constexpr size_t smem = dcn_smem_main() + 128 * sizeof(int);             // + the (ho, wo) table of the tile's rows
-  static MqOncePerDevice attr_set;
-  if (attr_set.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)dcn_igemm8_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dcn_igemm8_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)dcn_igemm8_kernel<16, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done();
-  }
-#if MQ_DCN_SPLIT
-  // split-precise: 8 waves (wave tile 64 x 64: the planar hi / lo fragments are twice the registers of the fp16 ones -- 16 waves at 128 VGPRs spill)
-  static const int nw = [] { const char* e = getenv("MQ_DCN_WAVES"); return (e && e[0] == '1') ? 16 : 8; }();
-#else
-  static const int nw = [] { const char* e = getenv("MQ_DCN_WAVES"); return (e && e[0] == '8') ? 8 : 16; }();   // A/B switch
-#endif
   const dim3 grid((unsigned)(8 * ((g.tiles_all + 7) / 8)));
 #ifdef MQ_PRIMARY_UNIT
   if (const int abl = (br[0].flags >> 8) & 15) {             // ablation timings (tools/microbench.py)
     switch (abl) {
-#define MQ_DCN_ABL(A_)                                                                                                             \
-      case A_: {                                                                                                                   \
-        hipError_t e = hipFuncSetAttribute((const void*)dcn_igemm8_kernel<16, A_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        if (e != hipSuccess) return (int)e;                                                                                        \
-        hipLaunchKernelGGL((dcn_igemm8_kernel<16, A_>), grid, dim3(1024), smem, (hipStream_t)stream, g);                            \
-        break;                                                                                                                     \
-      }
+#define MQ_DCN_ABL(A_) case A_: return mq_launch<dcn_igemm8_kernel<16, A_>>(grid, dim3(1024), smem, (hipStream_t)stream, g);
       MQ_DCN_ABL(1) MQ_DCN_ABL(2) MQ_DCN_ABL(3) MQ_DCN_ABL(4) MQ_DCN_ABL(8) MQ_DCN_ABL(7) MQ_DCN_ABL(15)
 #undef MQ_DCN_ABL
       default: return -4;
     }
-    MQ_CHECK_LAUNCH();
-    return 0;
   }
 #endif
-  // one barrier per k-step by default since GPU calls 14 / 15 of round 3 (0.661 - 0.668 ms against 0.673 - 0.692 with two, three of three
-  // comparisons; equal outputs); MQ_DCN_SYNC=2: the former schedule (A/B switch)
+  // The A/B switches, read once per process.  MQ_DCN_WAVES: the other wave count of this build (16-bit: 8 -- wave tiles of 64 x 64, a third fewer
+  // fragment reads per k-step; split-precise: 1 -> 16).  MQ_DCN_SYNC=2: two barriers per k-step, the schedule before GPU calls 14 / 15 of round 3
+  // (0.661 - 0.668 ms with one against 0.673 - 0.692 with two, three of three comparisons; equal outputs).  MQ_DCN_PLAIN=0: no PLAIN instantiations.
+  static const int nw = [] { const char* e = getenv("MQ_DCN_WAVES"); return MQ_SPLIT_OPERANDS ? ((e && e[0] == '1') ? 16 : 8) : ((e && e[0] == '8') ? 8 : 16); }();
   static const int sync = [] { const char* e = getenv("MQ_DCN_SYNC"); return (e && e[0] == '2') ? 2 : 1; }();
-  bool plain = true;                                          // flags bit 1 on EVERY branch: zero offsets, mask 1 (the caller's promise)
-  for (int i = 0; i < n; ++i) plain = plain && (br[i].B <= 0 || (br[i].flags & 2));
-  static const bool plain_on = [] { const char* e = getenv("MQ_DCN_PLAIN"); return !(e && e[0] == '0'); }();   // A/B switch
-  {
-    // flags bit 2 on EVERY branch: the weights are in LDS-tile order (ops.dcn_weight_tiles) -> the BDMA instantiations
-    int nb = 0, nt = 0;
-    for (int i = 0; i < n; ++i) if (br[i].B > 0) { ++nb; nt += (br[i].flags >> 2) & 1; }
-    if (nt != 0 && nt != nb) return -5;
-    if (nt) {
-      constexpr int BW = MQ_DCN_SPLIT ? 8 : 16;               // waves of the shipped instantiation of this build
-      int rc;
-#if !MQ_DCN_SPLIT
-      if (nw == 8)                                            // A/B switch MQ_DCN_WAVES=8: wave tiles of 64 x 64 (a third fewer fragment reads per k-step)
-        rc = (plain && plain_on) ? dcn_launch<8, 1, true, true>(grid, smem, (hipStream_t)stream, g) : dcn_launch<8, 1, false, true>(grid, smem, (hipStream_t)stream, g);
-      else
-#endif
-      rc = (plain && plain_on) ? dcn_launch<BW, 1, true, true>(grid, smem, (hipStream_t)stream, g)
-                               : dcn_launch<BW, 1, false, true>(grid, smem, (hipStream_t)stream, g);
-      if (rc) return rc;
-      MQ_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-#if MQ_DCN_SPLIT
-  if (nw == 8) {                                              // split-precise default: 8 waves, one barrier per k-step, PLAIN for the FPN convs
-    int rc;
-    if (plain && plain_on) rc = dcn_launch<8, 1, true>(grid, smem, (hipStream_t)stream, g);
-    else if (sync == 2) rc = dcn_launch<8, 2, false>(grid, smem, (hipStream_t)stream, g);
-    else rc = dcn_launch<8, 1, false>(grid, smem, (hipStream_t)stream, g);
-    if (rc) return rc;
-    MQ_CHECK_LAUNCH();
-    return 0;
-  }
-#endif
-  if (plain && plain_on && nw == 16 && sync == 1) {
-    static MqOncePerDevice attr_plain;
-    if (attr_plain.first()) {
-      hipError_t e = hipFuncSetAttribute((const void*)dcn_igemm8_kernel<16, 0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return (int)e;
-      attr_plain.done();
-    }
-    hipLaunchKernelGGL((dcn_igemm8_kernel<16, 0, 1, true>), grid, dim3(1024), smem, (hipStream_t)stream, g);
-  } else if (nw == 16 && sync == 1) hipLaunchKernelGGL((dcn_igemm8_kernel<16, 0, 1>), grid, dim3(1024), smem, (hipStream_t)stream, g);
-  else if (nw == 16) hipLaunchKernelGGL(dcn_igemm8_kernel<16>, grid, dim3(1024), smem, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(dcn_igemm8_kernel<8>, grid, dim3(512), smem, (hipStream_t)stream, g);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  static const bool plain_on = [] { const char* e = getenv("MQ_DCN_PLAIN"); return !(e && e[0] == '0'); }();
+  // flags bit 1 on EVERY branch: zero offsets, mask 1 (the caller's promise); flags bit 2 on EVERY branch: the weights are in LDS-tile order
+  // (ops.dcn_weight_tiles) -> the BDMA instantiations; on some only: -5
+  bool plain = true;
+  int nb = 0, nt = 0;
+  for (int i = 0; i < n; ++i) if (br[i].B > 0) { ++nb; plain = plain && (br[i].flags & 2); nt += (br[i].flags >> 2) & 1; }
+  if (nt != 0 && nt != nb) return -5;
+  return dcn_launch(dcn_pick(nw, sync, plain && plain_on, nt != 0), grid, smem, (hipStream_t)stream, g);
 }
 
 extern "C" int MQ_SYM(mq_dcnv2_fwd)(const void* x, const float* om, const void* w, const void* bias, void* out, float* stats,

@@ -45,16 +45,6 @@ struct GcpAttnParams {
   float eps, scale;
 };
 
-template <int I, int N, class F>
-__device__ __forceinline__ void gf_static_for_impl(F& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    gf_static_for_impl<I + 1, N>(f);
-  }
-}
-template <int N, class F>
-__device__ __forceinline__ void gf_static_for(F f) { gf_static_for_impl<0, N>(f); }
-
 // acc[mb][j] += A(rows of this block, K) . W(rows = this wave's 16 j-th output columns, K)^T over NG groups of G k-steps of 32 (K = 32 G NG).
 // At: LDS, lane's fragment base (row l15, k offset 8 lg); wrow[j]: global, the lane's 8 elements of the first k-step of its j-th 16-column tile in
 // the FRAGMENT-ORDER weights (mqdet_hip.h "MFMA B-fragment order": [N / 16][K / 32][64 lanes][8], k-step stride GF_WKS): one wave instruction
@@ -77,11 +67,11 @@ __device__ __forceinline__ void gf_rows_gemm(const half_t* At, const half_t* con
       }
     __builtin_amdgcn_sched_barrier(0);
   };
-  gf_static_for<NSETS - 1>([&](auto sc) __attribute__((always_inline)) {
+  mq_static_for<NSETS - 1>([&](auto sc) __attribute__((always_inline)) {
     constexpr int s = decltype(sc)::value;
     if constexpr (s < NG) load(w[s], s);
   });
-  gf_static_for<NG>([&](auto gc) __attribute__((always_inline)) {
+  mq_static_for<NG>([&](auto gc) __attribute__((always_inline)) {
     constexpr int grp = decltype(gc)::value;
     if constexpr (grp + NSETS - 1 < NG) load(w[(grp + NSETS - 1) % NSETS], grp + NSETS - 1);
 #pragma unroll
@@ -358,15 +348,7 @@ template <int MB, int ABL = 0>
 static int launch_gcp_attn(const GcpAttnParams& p, hipStream_t stream) {
   constexpr int RB = 16 * MB;
   constexpr size_t smem = (size_t)2 * RB * GF_P * sizeof(half_t) + (size_t)(GF_NW + 1) * RB * sizeof(float);
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gcp_attn_kernel<MB, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
-  hipLaunchKernelGGL((gcp_attn_kernel<MB, ABL>), dim3((unsigned)((p.M + RB - 1) / RB)), dim3(GF_NT), smem, stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<gcp_attn_kernel<MB, ABL>>(dim3((unsigned)((p.M + RB - 1) / RB)), dim3(GF_NT), smem, stream, p);
 }
 
 // x [B*T, 768] fp32 (the text residual stream), x_out the same shape (may alias x), y [B*T, 768] 16-bit = LN_f(x_out) or NULL, gate_out [B*T] or

@@ -163,15 +163,7 @@ template <int SLOTS>
 static int launch_sweep2(const unsigned long long* mask, const int* nvalid, unsigned char* keep, int B, int N, int col_blocks, int max_keep,
                          hipStream_t stream) {
   const size_t smem = (size_t)3 * 64 * col_blocks * sizeof(unsigned long long);
-  static MqMaxPerDevice attr_set;
-  if (attr_set.need(smem)) {
-    hipError_t e = hipFuncSetAttribute((const void*)nms2_sweep_kernel<SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done(smem);
-  }
-  hipLaunchKernelGGL((nms2_sweep_kernel<SLOTS>), dim3(B), dim3(320), smem, stream, mask, nvalid, keep, N, col_blocks, max_keep);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<nms2_sweep_kernel<SLOTS>>(dim3(B), dim3(320), smem, stream, mask, nvalid, keep, N, col_blocks, max_keep);
 }
 
 // boxes [B,N,4] fp32 sorted by score (descending) per image, labels [B,N] int32, nvalid [B] int32, workspace of mq_ml_nms_workspace_bytes(B, N)

@@ -401,16 +401,7 @@ extern "C" int mq_post_sort_fwd(const float* boxes, const float* scores, const i
   for (int l = 0; l <= PS_MAXLVL; ++l) p.off[l] = off[l < NL ? l : NL];
   p.NL = NL; p.tot = tot;
   const size_t smem = (size_t)tot * sizeof(float);
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)post_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * SORT_MAX * sizeof(float)));
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
-  hipLaunchKernelGGL(post_merge_kernel, dim3((unsigned)B), dim3(PS_NT), smem, (hipStream_t)stream, boxes, scores, labels, boxes_o, scores_o,
-                     labels_o, nvalid, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<post_merge_kernel>(dim3((unsigned)B), dim3(PS_NT), smem, (hipStream_t)stream, boxes, scores, labels, boxes_o, scores_o, labels_o, nvalid, p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -41,15 +41,11 @@ struct SwinMlp2Params {
 // SPLIT (ops.swin_mlp2_pack under the precise mode): every 512-element fragment block is [hi: 64 lanes x 8 fp16 | lo: 64 lanes x 8 fp16] -- the same
 // 2 KB as the fp32 block -- staged by two linear LDS-DMA pieces and read back as one ds_read_b128 per plane; the LayerNorm fragments are split once
 // per wave, the GELU output once per hidden chunk.  No conversion arithmetic is left beside the weight stream.
-#if defined(MQ_F32) && !defined(MQ_F32_EXACT)
-#define MQ_SW_SPLIT 1
-typedef mq_split8 wfrag_t;
-__device__ __forceinline__ wfrag_t sw_frag(half8 x) { return mq_split(x); }
-__device__ __forceinline__ float4_ sw_mfma(const wfrag_t& a, const wfrag_t& b, float4_ c) { return mfma16_split(a, b, c); }
+#if MQ_SPLIT_OPERANDS
 // fragment of lane `lane` out of a planar block (LDS or global): hi at fp16 index 8 lane, lo 512 fp16 further
-__device__ __forceinline__ wfrag_t sw_wfrag(const half_t* blk, int lane) {
+__device__ __forceinline__ mq_frag sw_wfrag(const half_t* blk, int lane) {
   const _Float16* h = (const _Float16*)blk + lane * 8;
-  wfrag_t f;
+  mq_frag f;
   f.hi = *(const mq_h16x8*)h;
   f.lo = *(const mq_h16x8*)(h + 512);
   return f;
@@ -57,10 +53,6 @@ __device__ __forceinline__ wfrag_t sw_wfrag(const half_t* blk, int lane) {
 #define SW_LANE8 0                       // the lane offset is applied inside sw_wfrag (fp16 units of a plane)
 #define SW_WFRAG(ptr) sw_wfrag((ptr), lane)
 #else
-#define MQ_SW_SPLIT 0
-typedef half8 wfrag_t;
-#define sw_frag(x) (x)
-#define sw_mfma(a, b, c) mfma16((a), (b), (c))
 #define SW_LANE8 (lane * 8)              // 16-bit builds: token for token the round-5 expressions (tools/isa_diff.py: identical ISA)
 #define SW_WFRAG(ptr) (*(const half8*)(ptr))
 #endif
@@ -77,17 +69,6 @@ __device__ __forceinline__ float gelu_erf2(float v) {
   const float hv = 0.5f * v;
   return fmaf(hv, __builtin_copysignf(erf_abs_scaled(v), v), hv);
 }
-
-// compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_impl(F& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for_impl<I + 1, N>(f);
-  }
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F f) { static_for_impl<0, N>(f); }
 
 // GELU piece q of an iteration (8 values x GS stages in stage-diagonal order: value k = d - stage on diagonal d, so that a value's
 // stages are a few steps apart): its value index (want_k) or its stage
@@ -159,8 +140,8 @@ __device__ __forceinline__ void ln_fragments(const SwinMlp2Params& p, long row0,
 template <int C, int NW, bool TABLE>
 // (split-precise: the planar fragments are twice the registers and the weight rings twice the LDS -- C = 96: two workgroups per SIMD set, C = 192:
 // one, which the 100 KB of its rings allow anyway)
-__global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96 ? 4 : C <= 192 ? 3 : 2)) void swin_mlp2_kernel(SwinMlp2Params p) {
-  static_assert(!(MQ_SW_SPLIT && C >= 384) || NW == 4, "split-precise C = 384: four waves (one per SIMD)");
+__global__ __launch_bounds__(64 * NW, MQ_SPLIT_OPERANDS ? (C <= 96 ? 2 : 1) : (C <= 96 ? 4 : C <= 192 ? 3 : 2)) void swin_mlp2_kernel(SwinMlp2Params p) {
+  static_assert(!(MQ_SPLIT_OPERANDS && C >= 384) || NW == 4, "split-precise C = 384: four waves (one per SIMD)");
   constexpr int NT = 64 * NW, BM = 16 * NW, HID = 4 * C, KS = C / 32, CT = C / 16, NCHUNK = HID / 32;
   constexpr int FR = 512;                                     // halfs per fragment block (64 lanes x 8)
   constexpr int W1_FR = 2 * KS, W2_FR = CT, IT_FR = W1_FR + W2_FR;   // fragment blocks of one chunk of W1 / W2 / staged per iteration
@@ -170,7 +151,7 @@ __global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96
   // (48 KB): chunk j is loaded at the END of iteration j -- behind the barrier that says everybody has read chunk j - 1 -- and waited for before
   // iteration j + 1 starts: one exposed L2 -> LDS copy of 48 KB per iteration, against streaming ALL weights from L2 for every 16 tokens (the
   // tail kernel, which is what round 5's precise mode ran this width through: 1.04 ms per launch).
-  constexpr bool W2ONE = MQ_SW_SPLIT && C >= 384;
+  constexpr bool W2ONE = MQ_SPLIT_OPERANDS && C >= 384;
   constexpr int NS2 = W2ONE ? 1 : NS;
   static_assert(C % 32 == 0 && IT_FR % NW == 0 && NCHUNK % U == 0, "tile shapes");
   static_assert(!W2ONE || (W1_FR % NW == 0 && W2_FR % NW == 0), "per-ring staging");
@@ -195,7 +176,7 @@ __global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96
       const mq_rsrc rs = f < W1_FR ? rs_w1 : rs_w2;
       const int eoff = f < W1_FR ? (c1 * W1_FR + f) * FR : (c2 * W2_FR + (f - W1_FR)) * FR;
       half_t* dst = f < W1_FR ? w1s + (s1 * W1_FR + f) * FR : w2s + (s2 * W2_FR + (f - W1_FR)) * FR;
-#if MQ_SW_SPLIT
+#if MQ_SPLIT_OPERANDS
       // the 2 KB planar block as two linear 1 KB LDS-DMA pieces (hi plane, lo plane): asynchronous like the 16-bit builds' one piece
       lds_stage_16b_buf(rs, eoff * (int)sizeof(half_t), lane * 16, dst);
       lds_stage_16b_buf(rs, eoff * (int)sizeof(half_t) + 1024, lane * 16, (char*)dst + 1024);
@@ -210,7 +191,7 @@ __global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96
 #pragma unroll
     for (int i = 0; i < nb / NW; ++i) {
       const int f = wave + i * NW;
-#if MQ_SW_SPLIT
+#if MQ_SPLIT_OPERANDS
       char* dst = (char*)(l + f * FR);
       lds_stage_16b_buf(rs, (g0 + f * FR) * (int)sizeof(half_t), lane * 16, dst);
       lds_stage_16b_buf(rs, (g0 + f * FR) * (int)sizeof(half_t) + 1024, lane * 16, dst + 1024);
@@ -242,13 +223,13 @@ __global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96
     }
   }
 
-#if MQ_SW_SPLIT
-  wfrag_t xf[KS];
+#if MQ_SPLIT_OPERANDS
+  mq_frag xf[KS];
   {
     half8 xr[KS];
     if (p.delta) ln_fragments<C, true>(p, row0, l15, g, xr); else ln_fragments<C, false>(p, row0, l15, g, xr);
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) xf[ks] = sw_frag(xr[ks]);       // split once per wave
+    for (int ks = 0; ks < KS; ++ks) xf[ks] = mq_to_frag(xr[ks]);       // split once per wave
   }
 #else
   half8 xf[KS];
@@ -274,20 +255,20 @@ __global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96
     const half_t* a = w1s + st * W1_FR * FR + SW_LANE8;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      h[0] = sw_mfma(SW_WFRAG(a + ks * FR), xf[ks], h[0]);
-      h[1] = sw_mfma(SW_WFRAG(a + (KS + ks) * FR), xf[ks], h[1]);
+      h[0] = mq_frag_mfma(SW_WFRAG(a + ks * FR), xf[ks], h[0]);
+      h[1] = mq_frag_mfma(SW_WFRAG(a + (KS + ks) * FR), xf[ks], h[1]);
     }
   };
   // GEMM 2 (transposed) of one chunk from W2 stage `st`: OUT^T[C, 16 tokens] += W2p[:, 32 k-slots] . H^T (pipeline drain only)
   auto gemm2 = [&](int st, const half8& hf) {
     const half_t* a = w2s + st * W2_FR * FR + SW_LANE8;
-#if MQ_SW_SPLIT
-    const wfrag_t hs = sw_frag(hf);
+#if MQ_SPLIT_OPERANDS
+    const mq_frag hs = mq_to_frag(hf);
 #else
     const half8& hs = hf;
 #endif
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) acc2[ct] = sw_mfma(SW_WFRAG(a + ct * FR), hs, acc2[ct]);
+    for (int ct = 0; ct < CT; ++ct) acc2[ct] = mq_frag_mfma(SW_WFRAG(a + ct * FR), hs, acc2[ct]);
   };
 
   // ---- one pipelined iteration.  Its MFMAs form ONE sequence of N = 2 KS + CT steps that alternates GEMM1(chunk j + 1) -- a
@@ -358,33 +339,33 @@ __global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96
     const half_t* a1 = w1s + S1 * W1_FR * FR + SW_LANE8;      // W1 chunk j + 1 (for j = NCHUNK - 1: a zero chunk)
     const half_t* a2 = w2s + S2 * W2_FR * FR + SW_LANE8;      // W2 chunk j - 1
     // step i of the sequence: even -> GEMM1 fragment (hb = m & 1, ks = m >> 1), m = i / 2; odd -> GEMM2 fragment ct = i / 2
-    auto frag = [&](int i) __attribute__((always_inline)) -> wfrag_t {
+    auto frag = [&](int i) __attribute__((always_inline)) -> mq_frag {
       const int m = i >> 1;
       return (i & 1) ? SW_WFRAG(a2 + m * FR) : SW_WFRAG(a1 + ((m & 1) * KS + (m >> 1)) * FR);
     };
-#if MQ_SW_SPLIT
-    const wfrag_t hs_old = sw_frag(hf_old);                   // the GELU output of chunk j - 1, split once for its CT MFMAs
+#if MQ_SPLIT_OPERANDS
+    const mq_frag hs_old = mq_to_frag(hf_old);                   // the GELU output of chunk j - 1, split once for its CT MFMAs
 #else
     const half8& hs_old = hf_old;
 #endif
-    wfrag_t ring[RD];
+    mq_frag ring[RD];
     float gts[8], ges[8], gds[8];
 #pragma unroll
     for (int i = 0; i < RD && i < N; ++i) ring[i] = frag(i);
-    static_for<N>([&](auto ic) __attribute__((always_inline)) {
+    mq_static_for<N>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
-      static_for<NPIECE>([&](auto qc) __attribute__((always_inline)) {                       // the GELU pieces of this step: piece q belongs to step q N / NPIECE
+      mq_static_for<NPIECE>([&](auto qc) __attribute__((always_inline)) {                       // the GELU pieces of this step: piece q belongs to step q N / NPIECE
         constexpr int q = decltype(qc)::value;
         if constexpr (q * N / NPIECE == i)
           gelu_piece(std::integral_constant<int, gelu_piece_of(q, GS, true)>{}, std::integral_constant<int, gelu_piece_of(q, GS, false)>{},
                      hin, hf_new, gts, ges, gds);
       });
-      const wfrag_t a = ring[i % RD];
+      const mq_frag a = ring[i % RD];
       if constexpr (!(i & 1)) {
         constexpr int m = i >> 1;
-        hout[m & 1] = sw_mfma(a, xf[m >> 1], hout[m & 1]);
+        hout[m & 1] = mq_frag_mfma(a, xf[m >> 1], hout[m & 1]);
       } else {
-        acc2[i >> 1] = sw_mfma(a, hs_old, acc2[i >> 1]);
+        acc2[i >> 1] = mq_frag_mfma(a, hs_old, acc2[i >> 1]);
       }
       if constexpr (i + RD < N) ring[i % RD] = frag(i + RD);
       __builtin_amdgcn_sched_barrier(0);
@@ -404,7 +385,7 @@ __global__ __launch_bounds__(64 * NW, MQ_SW_SPLIT ? (C <= 96 ? 2 : 1) : (C <= 96
   gemm1(0, hA);                                               // pipeline fill: H^T of chunk 0
   __syncthreads();                                            // every wave is done with W1 stage 0 before chunk NS lands there
   for (int jb = 0; jb < NCHUNK; jb += U)                      // U iterations: every (stage phase, register set) combination once
-    static_for<U>([&](auto uc) __attribute__((always_inline)) {
+    mq_static_for<U>([&](auto uc) __attribute__((always_inline)) {
       constexpr int u = decltype(uc)::value;
       if constexpr (u % 2 == 0)
         step(jb + u, std::integral_constant<int, u % NS>{}, std::integral_constant<int, 0>{}, hA, hB, hfB, hfA);
@@ -507,13 +488,13 @@ __global__ __launch_bounds__(64 * NWT) void swin_mlp2_tail_kernel(SwinMlp2Params
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long row0 = (long)blockIdx.x * 16;
 
-#if MQ_SW_SPLIT
-  wfrag_t xf[KS];
+#if MQ_SPLIT_OPERANDS
+  mq_frag xf[KS];
   {
     half8 xr[KS];
     if (p.delta) ln_fragments<C, true>(p, row0, l15, g, xr); else ln_fragments<C, false>(p, row0, l15, g, xr);
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) xf[ks] = sw_frag(xr[ks]);       // split once per wave
+    for (int ks = 0; ks < KS; ++ks) xf[ks] = mq_to_frag(xr[ks]);       // split once per wave
   }
 #else
   half8 xf[KS];
@@ -527,15 +508,15 @@ __global__ __launch_bounds__(64 * NWT) void swin_mlp2_tail_kernel(SwinMlp2Params
   // fragment t of this wave's stream: chunk wave * CPW + t / N; within a chunk first W1 (hb = m & 1, ks = m >> 1), then W2 (ct)
   const half_t* w1 = p.w1f + (long)wave * CPW * W1_FR * FR + SW_LANE8;
   const half_t* w2 = p.w2f + (long)wave * CPW * W2_FR * FR + SW_LANE8;
-  auto frag = [&](int t) __attribute__((always_inline)) -> wfrag_t {
+  auto frag = [&](int t) __attribute__((always_inline)) -> mq_frag {
     const int cc = t / N, i = t % N;
     if (i < W1_FR) return SW_WFRAG(w1 + ((long)cc * W1_FR + (i & 1) * KS + (i >> 1)) * FR);
     return SW_WFRAG(w2 + ((long)cc * W2_FR + (i - W1_FR)) * FR);
   };
-  wfrag_t ring[RDT];
+  mq_frag ring[RDT];
 #pragma unroll
   for (int t = 0; t < RDT; ++t) ring[t] = frag(t);
-  static_for<CPW>([&](auto ccc) __attribute__((always_inline)) {
+  mq_static_for<CPW>([&](auto ccc) __attribute__((always_inline)) {
     constexpr int cc = decltype(ccc)::value;
     float4_ h[2];
     {
@@ -544,25 +525,25 @@ __global__ __launch_bounds__(64 * NWT) void swin_mlp2_tail_kernel(SwinMlp2Params
 #pragma unroll
       for (int r = 0; r < 4; ++r) { h[0][r] = (float)b0[r]; h[1][r] = (float)b1[r]; }
     }
-    static_for<W1_FR>([&](auto ic) __attribute__((always_inline)) {
+    mq_static_for<W1_FR>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value, t = cc * N + i;
-      h[i & 1] = sw_mfma(ring[t % RDT], xf[i >> 1], h[i & 1]);
+      h[i & 1] = mq_frag_mfma(ring[t % RDT], xf[i >> 1], h[i & 1]);
       if constexpr (t + RDT < CPW * N) ring[t % RDT] = frag(t + RDT);
       __builtin_amdgcn_sched_barrier(0);
     });
-#if MQ_SW_SPLIT
+#if MQ_SPLIT_OPERANDS
     half8 hf8;
 #pragma unroll
     for (int k = 0; k < 8; ++k) hf8[k] = (half_t)gelu_erf2(h[k >> 2][k & 3]);
-    const wfrag_t hf = sw_frag(hf8);
+    const mq_frag hf = mq_to_frag(hf8);
 #else
     half8 hf;
 #pragma unroll
     for (int k = 0; k < 8; ++k) hf[k] = (half_t)gelu_erf2(h[k >> 2][k & 3]);
 #endif
-    static_for<W2_FR>([&](auto ic) __attribute__((always_inline)) {
+    mq_static_for<W2_FR>([&](auto ic) __attribute__((always_inline)) {
       constexpr int ct = decltype(ic)::value, t = cc * N + W1_FR + ct;
-      acc2[ct] = sw_mfma(ring[t % RDT], hf, acc2[ct]);
+      acc2[ct] = mq_frag_mfma(ring[t % RDT], hf, acc2[ct]);
       if constexpr (t + RDT < CPW * N) ring[t % RDT] = frag(t + RDT);
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -650,34 +631,18 @@ static int device_cus() { return mq_device_cus(); }
 
 template <int C, int NW, bool TABLE>
 static int launch_swin_mlp2_main(const SwinMlp2Params& p, hipStream_t s) {
-  constexpr bool w2one = MQ_SW_SPLIT && C >= 384;           // (see swin_mlp2_kernel: one W2 stage)
+  constexpr bool w2one = MQ_SPLIT_OPERANDS && C >= 384;           // (see swin_mlp2_kernel: one W2 stage)
   constexpr size_t smem = (size_t)(2 * 2 * (C / 32) + (w2one ? 1 : 2) * (C / 16)) * 512 * sizeof(half_t) + (size_t)4 * C * sizeof(half_t) +
                           (TABLE ? MQ_GELU_TAB_N * 2 * sizeof(float) : 0);
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)swin_mlp2_kernel<C, NW, TABLE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
   constexpr int BM = 16 * NW;
   const unsigned grid = (unsigned)((p.M + BM - 1) / BM);
-  hipLaunchKernelGGL((swin_mlp2_kernel<C, NW, TABLE>), dim3(grid), dim3(64 * NW), smem, s, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<swin_mlp2_kernel<C, NW, TABLE>>(dim3(grid), dim3(64 * NW), smem, s, p);
 }
 
 template <int C, int NWT>
 static int launch_swin_mlp2_tail(const SwinMlp2Params& p, hipStream_t s) {
   constexpr size_t smem = (size_t)NWT * (NWT / 2) * 64 * sizeof(float4_) + (size_t)2 * NWT * 16 * sizeof(float);
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)swin_mlp2_tail_kernel<C, NWT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
-  hipLaunchKernelGGL((swin_mlp2_tail_kernel<C, NWT>), dim3((unsigned)((p.M + 15) / 16)), dim3(64 * NWT), smem, s, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<swin_mlp2_tail_kernel<C, NWT>>(dim3((unsigned)((p.M + 15) / 16)), dim3(64 * NWT), smem, s, p);
 }
 
 // WPC: workgroups of the main kernel a CU holds (its launch bounds / LDS).  The blocks beyond the last FULL pass go to the tail kernel
@@ -728,7 +693,7 @@ extern "C" int MQ_SYM(mq_swin_mlp2_fwd)(const float* x, const void* delta, const
   if (y && (!next_g || !next_b)) return -2;
   hipStream_t s = (hipStream_t)stream;
   switch (C) {
-#if MQ_SW_SPLIT
+#if MQ_SPLIT_OPERANDS
     // split-precise: workgroups per CU by the planar rings (48 / 96 / 150 KB of LDS) and the launch bounds; C = 384 with FOUR waves (64 tokens) per
     // workgroup: one wave per SIMD, the planar fragments of 12 k-steps + 24 accumulator tiles need more than 256 registers
     case 96: return dispatch_swin_mlp2<96, 4, 6, 2>(p, flags, s);

@@ -114,17 +114,8 @@ extern "C" int mq_tta_ingest_fwd(const unsigned char* src, const long* src_off, 
   if (TH < 1 || R < 1 || Hp < 1 || Wp < 1 || B > 65535) return -1;
   const size_t smem = (size_t)R * TTA_TW * 3;
   if (smem > 160 * 1024) return -1;
-  static MqMaxPerDevice attr_set;
-  if (attr_set.need(smem)) {
-    hipError_t e = hipFuncSetAttribute((const void*)tta_ingest_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done(smem);
-  }
   dim3 grid((Wp + TTA_TW - 1) / TTA_TW, (Hp + TH - 1) / TH, B);
-  hipLaunchKernelGGL(tta_ingest_kernel, grid, dim3(256), smem, (hipStream_t)stream, src, src_off, meta, bounds, coef, out, out_flip, err, Hp, Wp,
-                     TH, R, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], bgr, x255);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<tta_ingest_kernel>(grid, dim3(256), smem, (hipStream_t)stream, src, src_off, meta, bounds, coef, out, out_flip, err, Hp, Wp, TH, R, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], bgr, x255);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- merge

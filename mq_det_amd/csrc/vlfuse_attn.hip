@@ -33,17 +33,6 @@ MQ_NAMESPACE_BEGIN
 // reads are the native ds_read_b64_tr_b16 on each plane, the Q fragments are split once when they are loaded, the P fragments once per 32-key
 // step, and every contraction is three v_mfma_f32_16x16x32_f16 (mfma16_split).  One ring slot instead of two (the fp32 chunks of a tile are twice
 // the registers).
-#if defined(MQ_F32) && !defined(MQ_F32_EXACT)
-#define MQ_VL_SPLIT 1
-typedef mq_split8 vfrag;                   // an MFMA operand fragment: (hi, lo) fp16 x 8
-__device__ __forceinline__ vfrag vl_frag(half8 x) { return mq_split(x); }
-__device__ __forceinline__ float4_ vl_mfma(const vfrag& a, const vfrag& b, float4_ c) { return mfma16_split(a, b, c); }
-#else
-#define MQ_VL_SPLIT 0
-typedef half8 vfrag;
-__device__ __forceinline__ vfrag vl_frag(half8 x) { return x; }
-__device__ __forceinline__ float4_ vl_mfma(vfrag a, vfrag b, float4_ c) { return mfma16(a, b, c); }
-#endif
 
 namespace {
 constexpr int VH = 8, VD = 256;            // max heads (run-time count in the params), head dim
@@ -75,16 +64,6 @@ struct I2TParams {
 // half as many MFMAs, which the LDS still sustains).
 template <int NTH> struct TileRegs { half8 r[2048 / NTH]; };
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_u_impl(F& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for_u_impl<I + 1, N>(f);
-  }
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for_u(F f) { static_for_u_impl<0, N>(f); }
-
 // NCH: chunk rounds to do -- round i covers tile rows [i * NTH / 32, (i + 1) * NTH / 32): a tile whose tail rows nobody reads
 // (the last key / value tile of a caption that ends inside it) is staged only as far as it is read
 template <int NTH, int NCH = 2048 / NTH>
@@ -101,7 +80,7 @@ __device__ __forceinline__ void tile_commit(const TileRegs<NTH>& t, half_t* dst,
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     const int c = tid + i * NTH;
-#if MQ_VL_SPLIT
+#if MQ_SPLIT_OPERANDS
     const mq_split8 sp = mq_split(t.r[i]);                 // 8 fp32 operands -> 16 bytes into the hi plane, 16 into the lo plane
     _Float16* h = (_Float16*)dst + (c >> 5) * KS + (c & 31) * 8;
     *(mq_h16x8*)h = sp.hi;
@@ -117,19 +96,19 @@ __device__ __forceinline__ void tile_commit(const TileRegs<NTH>& t, half_t* dst,
 // on the block count of the LAST tile only); the others keep s = 0 and are masked by the caller -- a 141-token caption
 // fills 9 of the 12 blocks of its three 64-key tiles
 template <bool QLDS, int QB, int NBL = 4>
-__device__ __forceinline__ void qk_tile(const half_t* tile, const vfrag (&qf)[QB][8], const half_t* qw, float4_ (&s)[4][QB],
+__device__ __forceinline__ void qk_tile(const half_t* tile, const mq_frag (&qf)[QB][8], const half_t* qw, float4_ (&s)[4][QB],
                                         int l15, int lg) {
-  static_assert(!(MQ_VL_SPLIT && QLDS), "split-precise: the Q fragments live in registers (a planar Q tile does not fit beside the key tiles)");
+  static_assert(!(MQ_SPLIT_OPERANDS && QLDS), "split-precise: the Q fragments live in registers (a planar Q tile does not fit beside the key tiles)");
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) s[nb][qb] = (float4_){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int kk = 0; kk < VD / 32; ++kk) {
-    vfrag kf[4], qq[QB];
+    mq_frag kf[4], qq[QB];
 #pragma unroll
     for (int nb = 0; nb < NBL; ++nb) {
-#if MQ_VL_SPLIT
+#if MQ_SPLIT_OPERANDS
       const _Float16* kp = (const _Float16*)tile + (nb * 16 + l15) * KS + kk * 32 + lg * 8;
       kf[nb].hi = *(const mq_h16x8*)kp;
       kf[nb].lo = *(const mq_h16x8*)(kp + TILE);
@@ -139,7 +118,7 @@ __device__ __forceinline__ void qk_tile(const half_t* tile, const vfrag (&qf)[QB
     }
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
-#if !MQ_VL_SPLIT
+#if !MQ_SPLIT_OPERANDS
       if constexpr (QLDS) qq[qb] = *(const half8*)(qw + (qb * 16 + l15) * KS + kk * 32 + lg * 8);
       else
 #endif
@@ -148,7 +127,7 @@ __device__ __forceinline__ void qk_tile(const half_t* tile, const vfrag (&qf)[QB
 #pragma unroll
     for (int nb = 0; nb < NBL; ++nb)
 #pragma unroll
-      for (int qb = 0; qb < QB; ++qb) s[nb][qb] = vl_mfma(kf[nb], qq[qb], s[nb][qb]);
+      for (int qb = 0; qb < QB; ++qb) s[nb][qb] = mq_frag_mfma(kf[nb], qq[qb], s[nb][qb]);
   }
 }
 
@@ -158,20 +137,20 @@ template <int QB, int STL = 2>
 __device__ __forceinline__ void pv_tile(const half_t* tile, const half8 (&pf)[2][QB], float4_ (&o)[16][QB], int l15, int lg) {
 #pragma unroll
   for (int st = 0; st < STL; ++st) {
-#if MQ_VL_SPLIT
+#if MQ_SPLIT_OPERANDS
     const _Float16* base = (const _Float16*)tile + (st * 32 + 4 * lg + (l15 >> 2)) * KS + (l15 & 3) * 4;
-    vfrag pq[QB];
+    mq_frag pq[QB];
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) pq[qb] = mq_split(pf[st][qb]);      // once per 32-key step: feeds the 16 channel blocks below
 #pragma unroll
     for (int db = 0; db < 16; ++db) {
-      vfrag a;
+      mq_frag a;
       const mq_h16x4_t h0 = lds_read_tr16_h(base + db * 16), h1 = lds_read_tr16_h(base + 16 * KS + db * 16);
       const mq_h16x4_t l0 = lds_read_tr16_h(base + TILE + db * 16), l1 = lds_read_tr16_h(base + TILE + 16 * KS + db * 16);
 #pragma unroll
       for (int j = 0; j < 4; ++j) { a.hi[j] = h0[j]; a.hi[4 + j] = h1[j]; a.lo[j] = l0[j]; a.lo[4 + j] = l1[j]; }
 #pragma unroll
-      for (int qb = 0; qb < QB; ++qb) o[db][qb] = vl_mfma(a, pq[qb], o[db][qb]);
+      for (int qb = 0; qb < QB; ++qb) o[db][qb] = mq_frag_mfma(a, pq[qb], o[db][qb]);
     }
 #else
     const half_t* base = tile + (st * 32 + 4 * lg + (l15 >> 2)) * KS + (l15 & 3) * 4;
@@ -201,8 +180,8 @@ __device__ __forceinline__ void pv_tile(const half_t* tile, const half8 (&pf)[2]
 // room: 242 / 246 VGPRs, no spill) -- no Q tile in LDS, a fifth fewer fragment reads in the QK steps, tiles two steps ahead.
 template <int NT, int QB, int NBL, int ABL = 0, bool QREG = false>
 __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_i2t_kernel(I2TParams p) {
-  constexpr bool LEAN = NT >= 3 && !QREG && !MQ_VL_SPLIT;   // (split-precise: Q always in registers)
-  constexpr bool ONE = LEAN || MQ_VL_SPLIT;                // one ring slot: the next tile only
+  constexpr bool LEAN = NT >= 3 && !QREG && !MQ_SPLIT_OPERANDS;   // (split-precise: Q always in registers)
+  constexpr bool ONE = LEAN || MQ_SPLIT_OPERANDS;                // one ring slot: the next tile only
   constexpr int NTH = 2048 / (QB * 4), WR = 16 * QB;        // threads per workgroup (512 / 256), query rows per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   half_t* tiles = (half_t*)smem;                           // [2][TK][KS]   (split-precise: [2][hi | lo][TK][KS] fp16 -- the same bytes)
@@ -239,7 +218,7 @@ __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_i2t_kernel(I2TParams p
   }
   const float cl2 = p.clamp > 0.f ? p.clamp : 3.0e38f;                   // no clamp: a bound no logit reaches (one v_med3 either way)
 
-  vfrag qf[QB][8];
+  mq_frag qf[QB][8];
   const half_t* vb = p.v + (long)b * p.N * VD;
   const half_t* qw = Qs + wave * WR * KS;
   if constexpr (LEAN) {
@@ -253,7 +232,7 @@ __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_i2t_kernel(I2TParams p
     for (int qb = 0; qb < QB; ++qb) {
       const int row = min(row0 + qb * 16 + l15, p.N - 1);
 #pragma unroll
-      for (int kk = 0; kk < 8; ++kk) qf[qb][kk] = vl_frag(*(const half8*)(vb + (long)row * VD + kk * 32 + lg * 8));
+      for (int kk = 0; kk < 8; ++kk) qf[qb][kk] = mq_to_frag(*(const half8*)(vb + (long)row * VD + kk * 32 + lg * 8));
     }
   }
 
@@ -434,19 +413,11 @@ __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_i2t_kernel(I2TParams p
 
 template <int NT, int QB, int NBL, int ABL = 0, bool QREG = false>
 static int launch_i2t(const I2TParams& p, hipStream_t stream) {
-  constexpr size_t smem = (size_t)(2 * TILE + ((NT >= 3 && !QREG && !MQ_VL_SPLIT) ? BM * KS : 0)) * sizeof(half_t) + (size_t)2 * VH * NT * TK * sizeof(float);
+  constexpr size_t smem = (size_t)(2 * TILE + ((NT >= 3 && !QREG && !MQ_SPLIT_OPERANDS) ? BM * KS : 0)) * sizeof(half_t) + (size_t)2 * VH * NT * TK * sizeof(float);
   static_assert(4 * 32 * (VD + 8) <= 2 * TILE, "O staging must fit in the tiles");
-  static MqOncePerDevice attr_set;
-  if (attr_set.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)vlfuse_i2t_kernel<NT, QB, NBL, ABL, QREG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done();
-  }
   const int qtiles = (p.N + BM - 1) / BM;
   const long per = ((long)p.B * qtiles + 7) / 8;
-  hipLaunchKernelGGL((vlfuse_i2t_kernel<NT, QB, NBL, ABL, QREG>), dim3((unsigned)(8 * per)), dim3(2048 / (QB * 4)), smem, stream, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<vlfuse_i2t_kernel<NT, QB, NBL, ABL, QREG>>(dim3((unsigned)(8 * per)), dim3(2048 / (QB * 4)), smem, stream, p);
 }
 
 // (Round 3 built a PAIR-SPLIT variant of the image side: two waves share 32 query rows, each computes the logits of every second
@@ -544,7 +515,7 @@ __device__ __forceinline__ void vl_scoped_tiles(T* __restrict__ b0, T* __restric
 
 template <int QB, bool KM, int ABL = 0, bool TDMA = false>
 __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_t2i_kernel(T2IParams p) {
-  static_assert(!TDMA || (!MQ_VL_SPLIT && ABL == 0), "the LDS-copied tiles are the 16-bit builds' (the split-precise planes are computed while staging)");
+  static_assert(!TDMA || (!MQ_SPLIT_OPERANDS && ABL == 0), "the LDS-copied tiles are the 16-bit builds' (the split-precise planes are computed while staging)");
   constexpr int NTH = 2048 / (QB * 4), WR = 16 * QB;        // threads per workgroup (512 / 256), query rows per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   half_t* tiles = (half_t*)smem;                           // [2][TK][KS]
@@ -577,13 +548,13 @@ __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_t2i_kernel(T2IParams p
   const int t0 = split * tps, t1 = min(ntiles, t0 + tps);
   const int nt = max(t1 - t0, 0);
 
-  vfrag qf[QB][8];
+  mq_frag qf[QB][8];
   const half_t* qb_ = p.kf + (long)b * p.kv_bs + (long)h * p.kv_hs;
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const int row = min(row0 + qb * 16 + l15, p.T - 1);
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk) qf[qb][kk] = vl_frag(*(const half8*)(qb_ + (row * (int)p.kv_ts + kk * 32 + lg * 8)));
+    for (int kk = 0; kk < 8; ++kk) qf[qb][kk] = mq_to_frag(*(const half8*)(qb_ + (row * (int)p.kv_ts + kk * 32 + lg * 8)));
   }
   float4_ o[16][QB];
 #pragma unroll
@@ -599,7 +570,7 @@ __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_t2i_kernel(T2IParams p
   // (profiles/r03_call8_microbench_vlfuse.json) takes a third off the launch when the tile loads are removed -- but a third slot
   // (RS = 3) changed nothing (0.3202 vs 0.3218 ms, GPU call 9): it is the L2 -> CU ingest of 32 KB per tile and workgroup, not its
   // latency, that the loads cost.  Two slots.
-  constexpr int RS = TDMA ? 0 : MQ_VL_SPLIT ? 1 : 2;       // (split-precise: one slot -- a tile's fp32 chunks are twice the registers)
+  constexpr int RS = TDMA ? 0 : MQ_SPLIT_OPERANDS ? 1 : 2;       // (split-precise: one slot -- a tile's fp32 chunks are twice the registers)
   TileRegs<NTH> slot[RS > 0 ? RS : 1];
   // TDMA: pieces of a tile and this lane's source offsets (bytes inside a tile of 64 rows x 512 B)
   constexpr int NWV = NTH / 64, NPC = TK * KS * (int)sizeof(half_t) / 1024, PR = (NPC + NWV - 1) / NWV;
@@ -735,7 +706,7 @@ __global__ __launch_bounds__(2048 / (QB * 4)) void vlfuse_t2i_kernel(T2IParams p
   constexpr int U = RS == 3 ? 6 : 2;                       // lcm(2, RS) steps: every (buffer, slot) combination once
   for (int pos = 0; pos < nt; pos += U) {
     bool done = false;
-    static_for_u<U>([&](auto uc) __attribute__((always_inline)) {
+    mq_static_for<U>([&](auto uc) __attribute__((always_inline)) {
       constexpr int u = decltype(uc)::value;
       if (!done) {
         body(std::integral_constant<int, u & 1>{}, std::integral_constant<int, u % (RS > 0 ? RS : 1)>{}, pos + u, tiles + (u & 1) * TILE, tiles + ((u & 1) ^ 1) * TILE);
@@ -820,15 +791,6 @@ extern "C" int MQ_SYM(mq_vlfuse_t2i_fwd)(const void* kf, long kv_bs, long kv_hs,
   p.B = B; p.N = N; p.T = T; p.H = heads; p.nsplit = nsplit; p.clamp = clamp; p.wr = 16 * vlfuse_qb();
   p.kmask = key_mask; p.kmask_bs = key_mask_bs;
   constexpr size_t smem = (size_t)2 * TILE * sizeof(half_t);
-  static MqOncePerDevice attr_set;
-  if (attr_set.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)vlfuse_t2i_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vlfuse_t2i_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vlfuse_t2i_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)vlfuse_t2i_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set.done();
-  }
   // key / value tiles by LDS-DMA (default since GPU call 20 of round 6: 259.9 -> 238.0 us per launch, +0.9 % end to end); MQ_VL_T2I_DMA=0: register ring
   static const bool t2i_dma = [] { const char* e = getenv("MQ_VL_T2I_DMA"); return !(e && e[0] == '0'); }();
   (void)t2i_dma;
@@ -836,46 +798,33 @@ extern "C" int MQ_SYM(mq_vlfuse_t2i_fwd)(const void* kf, long kv_bs, long kv_hs,
   const int groups = B * nsplit, members = (heads * ((rows + p.wr - 1) / p.wr) + (128 / p.wr) - 1) / (128 / p.wr);
   p.members = members;
   const dim3 grid((unsigned)(8 * ((groups + 7) / 8) * members));
+  hipStream_t st = (hipStream_t)stream;
 #ifdef MQ_PRIMARY_UNIT
   if (variant >= 100 && !key_mask) {                                       // ablation timings (tools/microbench.py; results are garbage)
-    hipStream_t st = (hipStream_t)stream;
+    int rc;
     switch (variant - 100) {
-#define MQ_T2I_ABL(A_)                                                                                                              \
-      case A_: {                                                                                                                    \
-        hipError_t e = hipFuncSetAttribute((const void*)vlfuse_t2i_kernel<1, false, A_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        if (e != hipSuccess) return (int)e;                                                                                         \
-        hipLaunchKernelGGL((vlfuse_t2i_kernel<1, false, A_>), grid, dim3(512), smem, st, p);                                        \
-        break;                                                                                                                      \
-      }
+#define MQ_T2I_ABL(A_) case A_: rc = mq_launch<vlfuse_t2i_kernel<1, false, A_>>(grid, dim3(512), smem, st, p); break;
       MQ_T2I_ABL(1) MQ_T2I_ABL(3) MQ_T2I_ABL(4) MQ_T2I_ABL(8) MQ_T2I_ABL(11) MQ_T2I_ABL(15)
 #undef MQ_T2I_ABL
       default: return -4;
     }
-    MQ_CHECK_LAUNCH();
-    return 0;
+    return rc;
   }
 #endif
+  int rc;
   if (vlfuse_qb() == 1) {
-    if (key_mask) hipLaunchKernelGGL((vlfuse_t2i_kernel<1, true>), grid, dim3(512), smem, (hipStream_t)stream, p);
-#if !MQ_VL_SPLIT
-    else if (t2i_dma && (long)N * VD * (long)sizeof(half_t) < (1l << 31)) {
-      static MqOncePerDevice attr_dma;
-      if (attr_dma.first()) {
-        hipError_t e = hipFuncSetAttribute((const void*)vlfuse_t2i_kernel<1, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-        attr_dma.done();
-      }
-      hipLaunchKernelGGL((vlfuse_t2i_kernel<1, false, 0, true>), grid, dim3(512), smem, (hipStream_t)stream, p);
-    }
+    if (key_mask) rc = mq_launch<vlfuse_t2i_kernel<1, true>>(grid, dim3(512), smem, st, p);
+#if !MQ_SPLIT_OPERANDS
+    else if (t2i_dma && (long)N * VD * (long)sizeof(half_t) < (1l << 31)) rc = mq_launch<vlfuse_t2i_kernel<1, false, 0, true>>(grid, dim3(512), smem, st, p);
 #endif
-    else hipLaunchKernelGGL((vlfuse_t2i_kernel<1, false>), grid, dim3(512), smem, (hipStream_t)stream, p);
+    else rc = mq_launch<vlfuse_t2i_kernel<1, false>>(grid, dim3(512), smem, st, p);
   } else {
-    if (key_mask) hipLaunchKernelGGL((vlfuse_t2i_kernel<2, true>), grid, dim3(256), smem, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((vlfuse_t2i_kernel<2, false>), grid, dim3(256), smem, (hipStream_t)stream, p);
+    if (key_mask) rc = mq_launch<vlfuse_t2i_kernel<2, true>>(grid, dim3(256), smem, st, p);
+    else rc = mq_launch<vlfuse_t2i_kernel<2, false>>(grid, dim3(256), smem, st, p);
   }
-  MQ_CHECK_LAUNCH();
+  if (rc) return rc;
   const long total = (long)B * heads * T;
-  hipLaunchKernelGGL(vlfuse_t2i_combine_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(vlfuse_t2i_combine_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, p);
   MQ_CHECK_LAUNCH();
   return 0;
 }

@@ -229,17 +229,6 @@ struct WinQkvParams {
 // Split-precise build: every fragment that feeds more than one MFMA is split ONCE into (hi, lo) fp16 x 8 -- the X fragments of the window (kept for
 // all heads: the fp32 copy dies), the weight fragment of a (matrix, channel block, k-step), q / k / v of a head, the probabilities of a key step -- and
 // the MFMAs are mfma16_split: nothing is split twice, no fp32 copy stays live beside its split form.
-#if defined(MQ_F32) && !defined(MQ_F32_EXACT)
-#define MQ_WQ_SPLIT 1
-typedef mq_split8 wq_frag;
-#define WQ_F(x) mq_split(x)
-#define WQ_MFMA(a, b, c) mfma16_split((a), (b), (c))
-#else
-#define MQ_WQ_SPLIT 0
-typedef half8 wq_frag;
-#define WQ_F(x) (x)
-#define WQ_MFMA(a, b, c) mfma16((a), (b), (c))
-#endif
 // (split-precise build: the fp32 X fragments of a window and their split copies are twice the registers -- one workgroup per CU there: 256 VGPRs + 238
 // AGPRs and no scratch at C = 96 instead of 178 spilled VGPRs, 2.0 GB of scratch traffic per launch in profiles/r06_pmc_traffic_split.json)
 #if defined(MQ_F32)
@@ -299,7 +288,7 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
       return ry * 3 + rx;
     };
     // ---- X fragments: token blk * 16 + l15, channels 32 ks + 8 lg .. + 7; tokens >= N copy token N - 1 (masked as keys, not stored)
-    wq_frag xf[NB][KS];
+    mq_frag xf[NB][KS];
     int out_off[NB];                                       // element offset of the token's row (B * H * W * C < 2^31: checked by the host), -1: none
     int region_q[NB];
     {
@@ -316,7 +305,7 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
         out_off[blk] = (real && i < N && active) ? tok * C : -1;
         region_q[blk] = region_of(i);
       }
-#if MQ_WQ_SPLIT
+#if MQ_SPLIT_OPERANDS
       half8 xr[NB][KS];
 #pragma unroll
       for (int blk = 0; blk < NB; ++blk)
@@ -356,8 +345,8 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
       }
       const half_t* Wb = STREAM ? Ws + (seq & 1) * 96 * C : Ws;
       // ---- projections of this head.  m = 0 (q), 1 (k): transposed; 2 (v): plain.  bias: row (d) for q / k, column (d) for v
-      constexpr int WQ_RD = MQ_WQ_SPLIT ? 1 : 2;            // depth of the weight-fragment ring of the projections
-      wq_frag qf[NB], kf[NB], vf[NB / 2][2];                // vf[st][db]: V^T A-fragment of 32-key step st, channel block db
+      constexpr int WQ_RD = MQ_SPLIT_OPERANDS ? 1 : 2;            // depth of the weight-fragment ring of the projections
+      mq_frag qf[NB], kf[NB], vf[NB / 2][2];                // vf[st][db]: V^T A-fragment of 32-key step st, channel block db
       {
         // A / B fragment of weight rows (matrix m, channel block db) for k-step ks: row l15, channels 32 ks + 8 lg .. + 7
         auto wfrag = [&](int m, int db, int ks) __attribute__((always_inline)) -> half8 {
@@ -389,18 +378,18 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
               const int i = ks * 2 + db;
-              const wq_frag wf = WQ_F(wring[i % WQ_RD]);
+              const mq_frag wf = mq_to_frag(wring[i % WQ_RD]);
               if (i + WQ_RD < 2 * KS) wring[i % WQ_RD] = wfrag(m, (i + WQ_RD) & 1, (i + WQ_RD) >> 1);
 #pragma unroll
-              for (int tb = 0; tb < NB; ++tb) acc[db][tb] = WQ_MFMA(wf, xf[tb][ks], acc[db][tb]);
-              if constexpr (!MQ_WQ_SPLIT) __builtin_amdgcn_sched_barrier(0);      // source order = issue order (hipcc sinks the ring's reads to their uses)
+              for (int tb = 0; tb < NB; ++tb) acc[db][tb] = mq_frag_mfma(wf, xf[tb][ks], acc[db][tb]);
+              if constexpr (!MQ_SPLIT_OPERANDS) __builtin_amdgcn_sched_barrier(0);      // source order = issue order (hipcc sinks the ring's reads to their uses)
             }
 #pragma unroll
           for (int tb = 0; tb < NB; ++tb) {
             half8 f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) { f[r] = (half_t)acc[0][tb][r]; f[4 + r] = (half_t)acc[1][tb][r]; }
-            if (m == 0) qf[tb] = WQ_F(f); else kf[tb] = WQ_F(f);
+            if (m == 0) qf[tb] = mq_to_frag(f); else kf[tb] = mq_to_frag(f);
           }
           __builtin_amdgcn_sched_barrier(0);                 // one projection at a time: their accumulators must not be live together
         }
@@ -419,13 +408,13 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
 #pragma unroll
           for (int db = 0; db < 2; ++db) {
             const int i = ks * 2 + db;
-            const wq_frag wf = WQ_F(wring[i % WQ_RD]);
+            const mq_frag wf = mq_to_frag(wring[i % WQ_RD]);
             if (i + WQ_RD < 2 * KS) wring[i % WQ_RD] = wfrag(2, (i + WQ_RD) & 1, (i + WQ_RD) >> 1);
 #pragma unroll
-            for (int tb = 0; tb < NB; ++tb) acc[tb][db] = WQ_MFMA(xf[tb][ks], wf, acc[tb][db]);
-            if constexpr (!MQ_WQ_SPLIT) __builtin_amdgcn_sched_barrier(0);
+            for (int tb = 0; tb < NB; ++tb) acc[tb][db] = mq_frag_mfma(xf[tb][ks], wf, acc[tb][db]);
+            if constexpr (!MQ_SPLIT_OPERANDS) __builtin_amdgcn_sched_barrier(0);
           }
-#if MQ_WQ_SPLIT
+#if MQ_SPLIT_OPERANDS
 #pragma unroll
         for (int st = 0; st < NB / 2; ++st)
 #pragma unroll
@@ -451,7 +440,7 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
         if (qb * 16 >= N) break;
         float4_ s[NB];
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) s[nb] = WQ_MFMA(kf[nb], qf[qb], ((float4_){0.f, 0.f, 0.f, 0.f}));
+        for (int nb = 0; nb < NB; ++nb) s[nb] = mq_frag_mfma(kf[nb], qf[qb], ((float4_){0.f, 0.f, 0.f, 0.f}));
         const float* relq = rel + (qb * 16 + l15) * NP + 4 * lg;
         float4_ rb[NB];
 #pragma unroll
@@ -489,9 +478,9 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
           half8 pf;
 #pragma unroll
           for (int r = 0; r < 4; ++r) { pf[r] = (half_t)(s[2 * st][r] * inv); pf[4 + r] = (half_t)(s[2 * st + 1][r] * inv); }
-          const wq_frag ps = WQ_F(pf);
+          const mq_frag ps = mq_to_frag(pf);
 #pragma unroll
-          for (int db = 0; db < 2; ++db) o[db] = WQ_MFMA(vf[st][db], ps, o[db]);
+          for (int db = 0; db < 2; ++db) o[db] = mq_frag_mfma(vf[st][db], ps, o[db]);
         }
         if (out_off[qb] >= 0) {
 #pragma unroll
@@ -512,19 +501,11 @@ __global__ __launch_bounds__(256, MQ_WQKV_WG_PER_CU(STREAM)) void window_attn_qk
 template <int C, bool STREAM>
 static int launch_window_attn_qkv(const WinQkvParams& p, hipStream_t s) {
   constexpr size_t smem = (STREAM ? (size_t)2 * 96 * C : (size_t)3 * C * (C + 8)) * sizeof(half_t) + (size_t)3 * C * sizeof(half_t);
-  static MqOncePerDevice attr;
-  if (attr.first()) {
-    hipError_t e = hipFuncSetAttribute((const void*)window_attn_qkv_kernel<C, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr.done();
-  }
   int cus = 256, dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   const long wgs_needed = (p.windows + 3) / 4, slots = (long)cus * MQ_WQKV_WG_PER_CU(STREAM);  // persistent workgroups: as many as the chip holds
   const long wgs = wgs_needed < slots ? wgs_needed : slots;
-  hipLaunchKernelGGL((window_attn_qkv_kernel<C, STREAM>), dim3((unsigned)wgs), dim3(256), smem, s, p);
-  MQ_CHECK_LAUNCH();
-  return 0;
+  return mq_launch<window_attn_qkv_kernel<C, STREAM>>(dim3((unsigned)wgs), dim3(256), smem, s, p);
 }
 
 // x [B,H,W,C] 16-bit = norm1(x) on the UNPADDED tokens, w [3C, C] / bias [3C] = attn.qkv (nn.Linear layout), rel_bias as

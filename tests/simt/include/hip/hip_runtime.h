@@ -12,6 +12,8 @@
 #include <stddef.h>
 #include <string.h>
 #include <algorithm>
+#include <mutex>
+#include <vector>
 
 #define MQ_SIMT_EMULATION 1
 
@@ -40,7 +42,7 @@ namespace simt {
 struct Fiber;
 extern Fiber* cur;                                   // the fiber that is executing
 extern dim3 g_blockIdx, g_blockDim, g_gridDim;
-extern int g_error;
+extern thread_local int g_error;                   // the last error is per host thread, as in HIP
 const uint3_& tid();
 int lane();
 void* dyn_smem();
@@ -82,14 +84,36 @@ inline T shfl_idx(T v, int src) {
 #define warpSize 64
 
 inline hipError_t hipGetLastError() { int e = simt::g_error; simt::g_error = 0; return e; }
-template <class K>
-inline hipError_t hipFuncSetAttribute(K, hipFuncAttribute, int) { return hipSuccess; }
+// The current device of the calling host thread (0 unless a test sets it; an index outside 0..31 is answered as it is, g_device_error makes
+// the query fail), a log of every hipFuncSetAttribute (kernel, device, bytes), and a one-shot failure of the next such call on this thread:
+// what tests/simt/launch_selftest.cpp drives csrc/common.h's mq_launch with.
+namespace simt {
+inline thread_local int g_device = 0, g_device_error = 0, g_attr_fail_next = 0;
+struct AttrCall { const void* kernel; int device, bytes; };
+inline std::mutex g_attr_mutex;
+inline std::vector<AttrCall> g_attr_calls;
+inline int attr_calls(const void* kernel, int device, int* last_bytes = nullptr) {
+  std::lock_guard<std::mutex> lock(g_attr_mutex);
+  int n = 0;
+  for (const AttrCall& c : g_attr_calls)
+    if (c.kernel == kernel && c.device == device) { ++n; if (last_bytes) *last_bytes = c.bytes; }
+  return n;
+}
+}  // namespace simt
+inline hipError_t hipFuncSetAttribute(const void* kernel, hipFuncAttribute, int bytes) {
+  if (int e = simt::g_attr_fail_next) { simt::g_attr_fail_next = 0; return e; }
+  std::lock_guard<std::mutex> lock(simt::g_attr_mutex);
+  simt::g_attr_calls.push_back({kernel, simt::g_device, bytes});
+  return hipSuccess;
+}
 enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount = 1 };
-inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
+inline hipError_t hipGetDevice(int* d) { *d = simt::g_device; return simt::g_device_error; }
 // a "chip" of 4 compute units: the pass / tail split of mq_swin_mlp2_fwd is reachable with a few hundred tokens
 inline hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) { *v = 4; return hipSuccess; }
+#ifndef hipLaunchKernelGGL                               // (launch_selftest.cpp brings its own: a plain call, no fibers)
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
   simt::launch_fn(dim3(grid), dim3(block), (size_t)(shmem), [&]() { kernel(__VA_ARGS__); })
+#endif
 
 inline void __syncthreads() { simt::block_sync(); }
 template <class T> inline T __shfl_xor(T v, int mask, int width = 64) { (void)width; return simt::shfl_idx(v, simt::lane() ^ mask); }

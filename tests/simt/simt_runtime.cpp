@@ -57,7 +57,7 @@ struct Fiber {
 
 Fiber* cur = nullptr;
 dim3 g_blockIdx, g_blockDim, g_gridDim;
-int g_error = 0;
+thread_local int g_error = 0;
 
 static const size_t STACK = 512 << 10;
 static std::vector<Fiber> fibers;

@@ -674,6 +674,16 @@ def test_alternate_kernel_selection(dev):
     _isolated("alternate_kernel_selection")
 
 
+def test_dcn_switch_settings_run_and_match_the_restatement(dev, tmp_path):
+    """The device counterpart of the emulator test of the same name: every A/B switch of the DCNv2 dispatcher (tests/dcn_switches.py), one
+    process per setting, in sequence, each under its own time limit, stopping at the first that fails -- the instantiation each setting picks
+    runs on the device and matches the torch restatement.  Equal outputs only for one barrier per k-step against two (row-major weights)."""
+    import dcn_switches
+    outs = dcn_switches.run_settings("gpu", str(tmp_path), timeout=120)
+    for k in ("offsets_s1", "offsets_s2"):
+        assert torch.equal(outs["rowmajor"][k], outs["sync2_rowmajor"][k]), k
+
+
 # ------------------------------------------------------------------------------------------------ bf16 operands (configs[3])
 @pytest.fixture()
 def bf16():

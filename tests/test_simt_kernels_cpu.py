@@ -197,6 +197,52 @@ def test_dcn_barrier_schedules_are_equal():
     assert torch.equal(outs[0], outs[1]) and float(outs[0].float().abs().mean()) > 0.01
 
 
+def test_dcn_switch_settings_run_and_match_the_restatement(tmp_path):
+    """Every A/B switch of the DCNv2 dispatcher (tests/dcn_switches.py: default, MQ_DCN_WAVES=8, MQ_DCN_SYNC=2 on row-major weights,
+    MQ_DCN_PLAIN=0, row-major weights, MQ_DCN_RASTER=0), one process each: the instantiation it picks runs and matches the torch restatement.
+    Equal outputs only where test_dcn_barrier_schedules_are_equal states them: one barrier per k-step against two, here on the row-major
+    weights, where the switch actually changes the kernel."""
+    import dcn_switches
+    outs = dcn_switches.run_settings("cpu", str(tmp_path), timeout=600)
+    for k in ("offsets_s1", "offsets_s2"):
+        assert torch.equal(outs["rowmajor"][k], outs["sync2_rowmajor"][k]), k
+
+
+def _host_program(tmp_path, source, name, extra=()):
+    """Compile a stand-alone program of tests/simt with the emulation's compiler, flags and include path; -> its path."""
+    import subprocess
+    from simt import build_emu
+    exe = str(tmp_path / name)
+    r = subprocess.run([build_emu.CXX, *[f for f in build_emu.FLAGS if f != "-fPIC"], "-I", build_emu.CSRC, os.path.join(build_emu.HERE, source), *extra,
+                        "-pthread", "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return exe
+
+
+@pytest.mark.parametrize("mode", ["rules", "threads"])
+def test_mq_launch_rules(tmp_path, mode):
+    """csrc/common.h's mq_launch, the one place a kernel's dynamic-LDS limit is raised (tests/simt/launch_selftest.cpp): once per kernel and
+    device for equal sizes, again only when the size grows, kernels and devices independent, never for 0 bytes, every time on an unknown
+    device, a failing attribute call returned and retried without a launch, a launch error returned; and two host threads on two devices."""
+    import subprocess
+    exe = _host_program(tmp_path, "launch_selftest.cpp", "launch_selftest")
+    r = subprocess.run([exe] + (["threads"] if mode == "threads" else []), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-1000:]
+
+
+@pytest.mark.parametrize("defs", [(), ("-DMQ_F32",)], ids=["16bit", "split_precise"])
+def test_dcn_pick_matches_the_dispatch_table(tmp_path, defs):
+    """dcn_pick of csrc/dcn_fused.hip against the table it was written from, every (nw, sync, plain, plain_on, tiled), in the 16-bit and in
+    the split-precise build (tests/simt/dcn_pick_selftest.cpp)."""
+    import subprocess
+    from simt import build_emu
+    lib = build_emu.build()                      # the program includes the emulation's copy of the source and links the emulation's runtime
+    exe = _host_program(tmp_path, "dcn_pick_selftest.cpp", "dcn_pick_selftest",
+                        extra=[*defs, "-I", os.path.join(build_emu.BUILD, "src"), "-x", "none", lib, "-Wl,-rpath," + build_emu.BUILD])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-1000:]
+
+
 def test_fpn_topdown_fused_equals_interpolate_plus_add(kernels, monkeypatch):
     """mq_add_upsample_nearest (KERNELS["FPN_TOPDOWN_FUSED"] = 1) against F.interpolate(mode="nearest")
     + add on even and odd size pairs (the reference's top-down step, fpn.py:82-95): EQUAL outputs; and the Swin + FPN check with it on."""
