@@ -487,6 +487,24 @@ int mq_lvis_match(const int* pair_dt, const int* pair_gt, const unsigned char* p
 int mq_lvis_accumulate(const int* cat_off, const int* order, const unsigned long long* dt_bits, const int* num_gt, const double* rec_thr,
                        double* precision, double* recall, int K, void* stream);
 
+/* ---- COCO-style AP (csrc/coco_eval.hip, host side mq_det_amd/evaluation.py CocoAPEvaluator).  fp64 / fp32 / integer data only.
+ * mq_coco_match: pycocotools' COCOeval.evaluateImg for P (image, category) pairs.  pair_dt / pair_gt [P, 2] int32 = (first, count) of the pair's
+ *   detections (sorted by score, already cut to maxDets[-1] = 100; dt_box [*, 4] fp32 xywh) and ground truths (annotation-file order: gt_box [*, 4]
+ *   fp64 xywh, gt_area fp64 = the annotation's `area`, gt_crowd uint8 = iscrowd, gt_nz uint8 = id != 0); area_rng [4, 2] and iou_thr [10] fp64.
+ *   -> dt_bits [*, 2] uint64 per detection: bit area * 10 + threshold of word 0 = matched to a ground truth of non-zero id, of word 1 = ignored;
+ *   gt_count [P, 4] int32 = non-ignored ground truths per area range.  ws: uint8 [40, Ng] (Ng = ground truths in all), the taken flags of pairs
+ *   with more than 256 ground truths.
+ * mq_coco_accumulate: COCOeval.accumulate for K categories x 3 maxDets: the detections of category k are dt_bits rows
+ *   order[cat_off[k] .. cat_off[k + 1]) in the reference's order (score descending, image id, rank in the pair), of which maxDets entry m keeps
+ *   those with rank[row] < max_dets[m]; num_gt [K, 4] int32; rec_thr [101] fp64 -> precision [10, 101, K, 4, 3] and recall [10, K, 4, 3] fp64
+ *   (-1 where num_gt == 0).
+ * Replaces pycocotools cocoeval.py:122-420 (evaluate / computeIoU with bbIou / evaluateImg / accumulate) for iouType bbox. */
+int mq_coco_match(const int* pair_dt, const int* pair_gt, const float* dt_box, const double* gt_box, const double* gt_area,
+                  const unsigned char* gt_crowd, const unsigned char* gt_nz, const double* area_rng, const double* iou_thr,
+                  unsigned long long* dt_bits, int* gt_count, unsigned char* ws, int P, long Ng, void* stream);
+int mq_coco_accumulate(const int* cat_off, const int* order, const int* rank, const unsigned long long* dt_bits, const int* num_gt,
+                       const int* max_dets, const double* rec_thr, double* precision, double* recall, int K, void* stream);
+
 /* ---- Vision-query bank (csrc/query_bank.hip, host side mq_det_amd/query_bank.py QueryBank).  fp32 / integer data only.
  * The admission loop of generalized_vl_rcnn_new.py:269-287 (== groundingdino.py:401-421) for N candidates in one launch.  cand [N, D] fp32
  * (D = scales x channels); sorted_labels / order [N] int64 = the candidates' labels after ONE stable sort and the sort's permutation; workgroup b

@@ -15,7 +15,8 @@ exchanges them between ranks by pickling the whole dict through two all_gathers 
   * `by_cat`      the reference's `{category: [ {"image_id", "category_id", "bbox", "score"} ]}` view for the LVIS API.
 Image ids must be exactly representable in fp32 (< 2^24; LVIS / COCO ids are < 600 000).
 
-`LvisFixedAPEvaluator` computes the LVIS Fixed AP from that state on the device (csrc/lvis_eval.hip; DESIGN.md "LVIS Fixed AP")."""
+`LvisFixedAPEvaluator` computes the LVIS Fixed AP from that state on the device (csrc/lvis_eval.hip; DESIGN.md "LVIS Fixed AP").
+`CocoAPEvaluator` computes pycocotools' COCO AP (COCO / ODinW) from rows of the same kind (csrc/coco_eval.hip; DESIGN.md "COCO AP")."""
 import json
 import math
 import os
@@ -96,9 +97,10 @@ class FixedAPAccumulator:
         dist.all_gather_into_tensor(sizes, n, group=group)
         sizes = sizes.tolist()
         m = max(max(sizes), 1)
-        pad = torch.zeros(m, 7, dtype=torch.float32, device=self.device)
+        cols = self.rows.shape[1]
+        pad = torch.zeros(m, cols, dtype=torch.float32, device=self.device)
         pad[:len(self.rows)] = self.rows
-        out = torch.empty(world * m, 7, dtype=torch.float32, device=self.device)
+        out = torch.empty(world * m, cols, dtype=torch.float32, device=self.device)
         dist.all_gather_into_tensor(out, pad, group=group)
         self.rows = torch.cat([out[r * m:r * m + sizes[r]] for r in range(world)])     # concatenated, like the reference
 
@@ -335,4 +337,270 @@ class LvisFixedAPEvaluator:
             line = template.format(title, _type, iou, area, -1, grp, value)
             print(line)
             out.append(line)
+        return out
+
+
+# ====================================================================================================== COCO AP on the device
+_COCO_MAX_DETS = (1, 10, 100)
+# COCOeval.summarize's twelve lines: (ap, iouThr, areaRng, maxDets)
+_COCO_SPECS = [(1, None, "all", 100), (1, .5, "all", 100), (1, .75, "all", 100), (1, None, "small", 100), (1, None, "medium", 100),
+               (1, None, "large", 100), (0, None, "all", 1), (0, None, "all", 10), (0, None, "all", 100), (0, None, "small", 100),
+               (0, None, "medium", 100), (0, None, "large", 100)]
+_COCO_METRICS = ["AP", "AP50", "AP75", "APs", "APm", "APl"]          # COCOResults.METRICS["bbox"]
+
+
+class _ResultRows(FixedAPAccumulator):
+    """The accumulator's buffer and exchange for `results_dict`: rows [n, 8] = the seven columns + a mark that is 1 on the first row of one
+    image's prediction and 0 on the others, so that the running sum of the marks numbers the predictions in arrival order -- also after the
+    gather, which concatenates the ranks' rows in rank order.  Nothing is pruned: COCO keeps every detection until the per-pair cut."""
+
+    def __init__(self, device):
+        super().__init__(topk=0, device=device)
+        self.rows = torch.zeros(0, 8, dtype=torch.float32, device=self.device)
+
+    def append(self, rows):
+        self._pending.append(rows)
+        self._npending += len(rows)
+
+    def _prune(self, rows):
+        return rows
+
+
+class CocoAPEvaluator:
+    """The COCO / ODinW branch of the reference's engine/inference.py (:649-650 `results_dict.update`, :703-708 the gather, :749-763 `evaluate` ->
+    data/datasets/evaluation/coco/coco_eval.py `do_coco_evaluation`: `prepare_for_coco_detection`, pycocotools `COCOeval` for iou_type bbox,
+    `summarize_per_category`, `COCOResults`) with the detections kept as device rows: `update` resizes, converts and maps labels on the device,
+    `synchronize_between_processes` is `FixedAPAccumulator`'s fixed-shape exchange, `summarize()` groups with torch sorts, matches and
+    accumulates in csrc/coco_eval.hip and takes the twelve means in torch; one host sync.
+
+    gt: the reference's `dataset.coco` (only `.dataset` is read), a dict in COCO json format, or a path to such a json.
+    label_to_cat_id: the dataset's `contiguous_category_id_to_json_id`; default {i + 1: id} over the sorted category ids."""
+
+    def __init__(self, gt, device="cuda", label_to_cat_id=None):
+        if isinstance(gt, (str, os.PathLike)):
+            with open(gt) as f:
+                gt = json.load(f)
+        ds = gt if isinstance(gt, dict) else gt.dataset
+        self.device = torch.device(device)
+        self.acc = _ResultRows(self.device)
+        self.results = OrderedDict()
+        self.stats = []
+        self.eval = {}
+        self.iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+        self.rec_thrs = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+        self._ingest(ds)
+        if label_to_cat_id is None:
+            label_to_cat_id = {i + 1: c for i, c in enumerate(self.cat_ids)}
+        labels = sorted(label_to_cat_id)
+        self.lbl_keys = torch.from_numpy(_ids(labels, "label_to_cat_id")).to(self.device)
+        self.lbl_vals = torch.from_numpy(_ids([label_to_cat_id[k] for k in labels], "label_to_cat_id")).float().to(self.device)
+
+    # ------------------------------------------------------------------ ground truth, once
+    def _ingest(self, ds):
+        dev = self.device
+        imgs = {}
+        for img in ds["images"]:                       # COCO.createIndex: the last image of an id wins
+            imgs[img["id"]] = img
+        cats = {}
+        for c in ds["categories"]:
+            cats[c["id"]] = c
+        img_ids = _ids(sorted(imgs), "images.id")      # params.imgIds / catIds
+        cat_ids = _ids(sorted(cats), "categories.id")
+        K = len(cat_ids)
+        self.K = K
+        self.cat_ids = [int(c) for c in cat_ids]
+        self.cat_names = [cats[c].get("name", str(c)) for c in sorted(cats)]
+        self.img_size = {int(i): (imgs[i]["width"], imgs[i]["height"]) for i in sorted(imgs) if "width" in imgs[i] and "height" in imgs[i]}
+        img_pos = {int(i): n for n, i in enumerate(img_ids)}
+        cat_pos = {int(c): n for n, c in enumerate(cat_ids)}
+        anns = ds.get("annotations", [])
+        a_img = _ids([a["image_id"] for a in anns], "annotations.image_id")
+        a_cat = _ids([a["category_id"] for a in anns], "annotations.category_id")
+        a_id = np.asarray([a["id"] for a in anns], dtype=np.int64).reshape(-1)
+        if len(np.unique(a_id)) != len(a_id):
+            raise ValueError("annotations.id: ids must be unique")
+        a_area = np.asarray([a["area"] for a in anns], dtype=np.float64).reshape(-1)
+        a_box = np.asarray([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
+        a_crowd = np.asarray([bool(a.get("iscrowd", 0)) for a in anns], dtype=np.uint8).reshape(-1)
+        # getAnnIds(imgIds, catIds): images of the file, categories of the file
+        idx = np.nonzero(np.array([int(i) in img_pos and int(c) in cat_pos for i, c in zip(a_img, a_cat)], dtype=bool).reshape(-1))[0]
+        key = np.array([img_pos[int(a_img[j])] * K + cat_pos[int(a_cat[j])] for j in idx], dtype=np.int64)
+        o = np.argsort(key, kind="stable")                  # per pair in annotation-file order
+        idx, key = idx[o], key[o]
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev)       # noqa: E731
+        self.gt_key = t(key, torch.int64)
+        self.gt_box = t(a_box[idx].reshape(-1, 4), torch.float64)
+        self.gt_area = t(a_area[idx], torch.float64)
+        self.gt_crowd = t(a_crowd[idx], torch.uint8)
+        self.gt_nz = t(a_id[idx] != 0, torch.uint8)
+        self.img_ids_f = t(img_ids.astype(np.float64), torch.float64)
+        self.cat_ids_f = t(cat_ids.astype(np.float64), torch.float64)
+        self.area_rng_t = t(np.asarray(_AREA_RNG, np.float64), torch.float64)
+        self.iou_thr_t = t(self.iou_thrs, torch.float64)
+        self.rec_thr_t = t(self.rec_thrs, torch.float64)
+
+    # ------------------------------------------------------------------ the engine's calls
+    def update(self, predictions):
+        """predictions: {image id: BoxList} or an iterable of such pairs (original image ids; boxes at any size) -- `results_dict.update` and
+        `prepare_for_coco_detection` in one: resize to the ground-truth image's (width, height), convert("xywh") with the legacy +1, labels
+        through label_to_cat_id.  An image that arrives again replaces what it had, an empty list included (it then has no detections); a row
+        of an unknown label keeps its place with a NaN category and falls out with the categories the file lacks."""
+        dev = self.device
+        items = predictions.items() if isinstance(predictions, dict) else predictions
+        for image_id, bl in items:
+            iid = float(_ids([image_id], "predictions.image_id")[0])
+            n = len(bl)
+            r = torch.zeros(max(n, 1), 8, dtype=torch.float32, device=dev)
+            r[:, 0] = iid
+            r[0, 7] = 1.0
+            if n == 0:
+                r[0, 1] = math.nan
+                self.acc.append(r)
+                continue
+            size = self.img_size.get(int(iid))
+            bl = bl.to(dev)
+            if size is not None:                           # an image the ground truth lacks: summarize() refuses it
+                bl = bl.resize(size)
+            labels = bl.get_field("labels").to(dev).long()
+            if len(self.lbl_keys):
+                j = torch.searchsorted(self.lbl_keys, labels).clamp(max=len(self.lbl_keys) - 1)
+                r[:, 1] = torch.where(self.lbl_keys[j] == labels, self.lbl_vals[j], torch.full((), math.nan, device=dev))
+            else:
+                r[:, 1] = math.nan
+            r[:, 2] = bl.get_field("scores").to(dev).float()
+            r[:, 3:7] = bl.convert("xywh").bbox
+            self.acc.append(r)
+
+    def synchronize_between_processes(self, group=None, force=False):
+        self.acc.synchronize_between_processes(group, force)
+
+    # ------------------------------------------------------------------ evaluate + accumulate
+    def _rows(self):
+        """-> (rows, pair key, rank in the pair, unknown-image flag): per image the prediction that arrived last, the detections COCOeval._prepare
+        keeps (categories of the file), sorted by pair and within a pair by score (ties in results order), cut to maxDets[-1] per pair."""
+        acc, dev, K = self.acc, self.device, self.K
+        acc._fold()
+        rows = acc.rows
+        NI = len(self.img_ids_f)
+        img, cat = rows[:, 0].double(), rows[:, 1].double()
+        real = ~torch.isnan(cat)
+        known = torch.zeros(len(rows), dtype=torch.bool, device=dev)
+        ii = torch.zeros(len(rows), dtype=torch.int64, device=dev)
+        if NI:
+            ii = torch.searchsorted(self.img_ids_f, img).clamp(max=NI - 1)
+            known = self.img_ids_f[ii] == img
+        unknown = (real & ~known).any()                    # loadRes: results' image ids must be a subset of the ground truth's
+        block = torch.cumsum((rows[:, 7] > 0).long(), 0)
+        zero = torch.zeros((), dtype=torch.int64, device=dev)
+        last = torch.zeros(max(NI, 1), dtype=torch.int64, device=dev)
+        last.scatter_reduce_(0, torch.where(known, ii, zero), torch.where(known, block, zero), "amax", include_self=True)
+        ok = known & real & (block == last[ii])
+        ci = torch.zeros(len(rows), dtype=torch.int64, device=dev)
+        if K:
+            ci = torch.searchsorted(self.cat_ids_f, torch.where(real, cat, torch.zeros((), dtype=torch.float64, device=dev))).clamp(max=K - 1)
+            ok &= self.cat_ids_f[ci] == cat
+        else:
+            ok &= False
+        key = ii * K + ci
+        rows, key = rows[ok], key[ok]
+        o = torch.sort(rows[:, 2], descending=True, stable=True)[1]
+        o = o[torch.sort(key[o], stable=True)[1]]
+        rows, key = rows[o], key[o]
+        ar = torch.arange(len(rows), device=dev)
+        first = torch.ones(len(rows), dtype=torch.bool, device=dev)
+        first[1:] = key[1:] != key[:-1]
+        rank = ar - torch.cummax(torch.where(first, ar, torch.zeros((), dtype=torch.int64, device=dev)), 0)[0] if len(rows) else ar
+        keep = rank < _COCO_MAX_DETS[-1]
+        return rows[keep], key[keep], rank[keep], unknown
+
+    def evaluate(self):
+        """-> (precision [10, 101, K, 4, 3], recall [10, K, 4, 3]) fp64 on the device, as COCOeval.accumulate lays them out; also kept in
+        self.eval with the per-detection match bits (test hooks)."""
+        from . import ops
+        K, dev = self.K, self.device
+        rows, dkey, rank, unknown = self._rows()
+        pkey = torch.unique(torch.cat([self.gt_key, dkey]))                       # every (image, category) pair with a gt or a detection
+        i32 = lambda x: x.to(torch.int32)                                          # noqa: E731
+        ds, de = torch.searchsorted(dkey, pkey), torch.searchsorted(dkey, pkey, right=True)
+        gs, ge = torch.searchsorted(self.gt_key, pkey), torch.searchsorted(self.gt_key, pkey, right=True)
+        pair_dt = i32(torch.stack([ds, de - ds], 1)).contiguous()
+        pair_gt = i32(torch.stack([gs, ge - gs], 1)).contiguous()
+        dt_box = rows[:, 3:7].contiguous()
+        dt_bits, gt_count = ops.coco_match(pair_dt, pair_gt, dt_box, self.gt_box, self.gt_area, self.gt_crowd, self.gt_nz, self.area_rng_t,
+                                           self.iou_thr_t)
+        num_gt = torch.zeros(K, 4, dtype=torch.int64, device=dev)
+        if K:
+            num_gt.index_add_(0, pkey % K, gt_count.long())
+        # accumulate's order per category: score descending, ties by image id, then by the rank in the pair
+        dcat = dkey % K if K else dkey
+        o = torch.sort(rows[:, 2], descending=True, stable=True)[1]
+        o = o[torch.sort(dcat[o], stable=True)[1]]
+        cat_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        cat_off[1:] = torch.cumsum(torch.bincount(dcat, minlength=K)[:K], 0)
+        precision, recall = ops.coco_accumulate(i32(cat_off), i32(o), i32(rank).contiguous(), dt_bits, i32(num_gt).contiguous(), self.rec_thr_t)
+        self.eval = {"precision": precision, "recall": recall, "pair_key": pkey, "pair_dt": pair_dt, "pair_gt": pair_gt, "dt_bits": dt_bits,
+                     "gt_count": gt_count, "num_gt": num_gt, "rows": rows, "rank": rank, "unknown_images": unknown}
+        return precision, recall
+
+    # ------------------------------------------------------------------ summary (COCOeval.summarize, COCOResults.update)
+    def _mean(self, s, iou_thr, area, max_det):
+        if iou_thr is not None:
+            s = s[torch.as_tensor(np.where(iou_thr == self.iou_thrs)[0], device=s.device)]
+        s = s[..., _AREA_LBL.index(area), _COCO_MAX_DETS.index(max_det)]
+        v = s > -1
+        n = v.sum()
+        return torch.where(n > 0, torch.where(v, s, torch.zeros((), dtype=s.dtype, device=s.device)).sum() / n.clamp(min=1),
+                           torch.full((), -1.0, dtype=torch.float64, device=s.device))
+
+    def summarize(self):
+        """Main process: the twelve lines COCOeval.summarize prints, self.stats and self.results["bbox"]; other ranks: None."""
+        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+            return None
+        precision, recall = self.evaluate()
+        vals = [self._mean(precision if ap else recall, thr, area, md) for ap, thr, area, md in _COCO_SPECS]
+        vals = torch.stack(vals + [self.eval["unknown_images"].double()]).cpu().tolist()          # the one host sync
+        if vals[-1]:
+            raise ValueError("Results do not correspond to current coco set: predictions of image ids the ground truth does not hold")
+        self.stats = [float(v) for v in vals[:-1]]
+        self.results = OrderedDict([("bbox", OrderedDict(zip(_COCO_METRICS, self.stats)))])
+        template = " {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}"
+        out = []
+        for (ap, thr, area, md), v in zip(_COCO_SPECS, self.stats):
+            iou = "{:0.2f}:{:0.2f}".format(self.iou_thrs[0], self.iou_thrs[-1]) if thr is None else "{:0.2f}".format(thr)
+            line = template.format("Average Precision" if ap else "Average Recall", "(AP)" if ap else "(AR)", iou, area, md, v)
+            print(line)
+            out.append(line)
+        return out
+
+    def per_category(self, csv_output=None):
+        """Main process: the lines of the reference's `summarize_per_category` (title, then AP / AP50 / APs / APm / APl at maxDets 100: the
+        per-category `np.mean` over thresholds and recall points, -1 entries included), also written to `csv_output` when given; other
+        ranks: None.  Not a hot path: the precision array comes to the host and numpy takes the means, so that the digits are numpy's."""
+        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+            return None
+        if "precision" not in self.eval:
+            self.evaluate()
+        precision = self.eval["precision"].cpu().numpy()
+        mind = [len(_COCO_MAX_DETS) - 1]
+
+        def line(iou_thr=None, area="all"):
+            iou = "{:0.2f}:{:0.2f}".format(self.iou_thrs[0], self.iou_thrs[-1]) if iou_thr is None else "{:0.2f}".format(iou_thr)
+            text = " {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ], ".format("Average Precision", "(AP)", iou, area, _COCO_MAX_DETS[-1])
+            s = precision
+            if iou_thr is not None:
+                s = s[np.where(iou_thr == self.iou_thrs)[0]]
+            s = s[:, :, :, [_AREA_LBL.index(area)], mind]
+            if len(s[s > -1]) == 0:
+                return text
+            avg = 0.0
+            for k in range(self.K):
+                text += "{}, ".format(np.mean(s[:, :, k, :]))
+                avg += np.mean(s[:, :, k, :])
+            return text + "{} \n".format(avg / self.K)
+        out = ["metric, " + "".join("{}, ".format(n) for n in self.cat_names) + "avg \n", line(), line(iou_thr=.5), line(area="small"),
+               line(area="medium"), line(area="large")]
+        if csv_output is not None:
+            with open(csv_output, "w") as f:
+                for text in out:
+                    f.writelines(text)
         return out

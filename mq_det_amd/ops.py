@@ -72,6 +72,8 @@ _SIGNATURES = {
     "mq_tta_merge_finalize": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
     "mq_lvis_match": (_i, [_vp] * 13 + [_i, _l, _vp]),
     "mq_lvis_accumulate": (_i, [_vp] * 7 + [_i, _vp]),
+    "mq_coco_match": (_i, [_vp] * 12 + [_i, _l, _vp]),
+    "mq_coco_accumulate": (_i, [_vp] * 9 + [_i, _vp]),
     "mq_bank_admit": (_i, [_vp] * 8 + [_i] * 8 + [_f, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
@@ -1612,6 +1614,50 @@ def lvis_accumulate(cat_off, order, dt_bits, num_gt, rec_thr, n_thr=10):
     with _timed("lvis_accumulate"):
         _chk(lib.mq_lvis_accumulate(_ptr(cat_off), _ptr(order), _ptr(dt_bits), _ptr(num_gt), _ptr(rec_thr), _ptr(precision), _ptr(recall), K,
                                     _stream()), "mq_lvis_accumulate")
+    return precision, recall
+
+
+# ---- COCO-style AP (csrc/coco_eval.hip; host side: mq_det_amd/evaluation.py CocoAPEvaluator)
+COCO_MAX_DETS = (1, 10, 100)
+
+
+def coco_match(pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_crowd, gt_nz, area_rng, iou_thr):
+    """evaluateImg for every pair -> (dt_bits [Nd, 2] int64 (uint64 bit patterns: matched, ignored; bit = area * 10 + threshold),
+    gt_count [P, 4] int32 non-ignored ground truths per area range).  Layouts: include/mqdet_hip.h mq_coco_match."""
+    lib = load_library()
+    _need_gpu(pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_crowd, gt_nz, area_rng, iou_thr)
+    assert pair_dt.dtype == pair_gt.dtype == torch.int32 and gt_crowd.dtype == gt_nz.dtype == torch.uint8
+    assert dt_box.dtype == torch.float32 and gt_box.dtype == gt_area.dtype == area_rng.dtype == iou_thr.dtype == torch.float64
+    assert area_rng.numel() == 8 and iou_thr.numel() == 10
+    for t in (pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_crowd, gt_nz):
+        assert t.is_contiguous()
+    P, Nd, Ng, dev = len(pair_dt), len(dt_box), len(gt_box), dt_box.device
+    assert len(pair_gt) == P and len(gt_area) == len(gt_crowd) == len(gt_nz) == Ng
+    dt_bits = torch.zeros(Nd, 2, dtype=torch.int64, device=dev)
+    gt_count = torch.zeros(P, 4, dtype=torch.int32, device=dev)
+    ws = torch.empty(LVIS_MATCH_LANES * max(Ng, 1), dtype=torch.uint8, device=dev)
+    with _timed("coco_match"):
+        _chk(lib.mq_coco_match(_ptr(pair_dt), _ptr(pair_gt), _ptr(dt_box), _ptr(gt_box), _ptr(gt_area), _ptr(gt_crowd), _ptr(gt_nz),
+                               _ptr(area_rng), _ptr(iou_thr), _ptr(dt_bits), _ptr(gt_count), _ptr(ws), P, Ng, _stream()), "mq_coco_match")
+    return dt_bits, gt_count
+
+
+def coco_accumulate(cat_off, order, rank, dt_bits, num_gt, rec_thr):
+    """accumulate -> (precision [10, 101, K, 4, 3], recall [10, K, 4, 3]) fp64, maxDets = COCO_MAX_DETS.  Layouts: include/mqdet_hip.h
+    mq_coco_accumulate."""
+    lib = load_library()
+    _need_gpu(cat_off, order, rank, dt_bits, num_gt, rec_thr)
+    assert cat_off.dtype == order.dtype == rank.dtype == num_gt.dtype == torch.int32 and dt_bits.dtype == torch.int64
+    assert rec_thr.dtype == torch.float64 and rec_thr.numel() == 101 and num_gt.is_contiguous() and dt_bits.is_contiguous()
+    assert len(rank) == len(dt_bits) and len(order) <= len(dt_bits)
+    K, dev = len(cat_off) - 1, dt_bits.device
+    assert num_gt.numel() == 4 * K
+    max_dets = torch.tensor(COCO_MAX_DETS, dtype=torch.int32).to(dev)
+    precision = torch.empty(10, 101, K, 4, 3, dtype=torch.float64, device=dev)
+    recall = torch.empty(10, K, 4, 3, dtype=torch.float64, device=dev)
+    with _timed("coco_accumulate"):
+        _chk(lib.mq_coco_accumulate(_ptr(cat_off), _ptr(order), _ptr(rank), _ptr(dt_bits), _ptr(num_gt), _ptr(max_dets), _ptr(rec_thr),
+                                    _ptr(precision), _ptr(recall), K, _stream()), "mq_coco_accumulate")
     return precision, recall
 
 

@@ -99,3 +99,56 @@ def synthetic_lvis(n_img=4809, n_cat=1203, n_gt=50000, det_per_cat=10000, seed=0
         r[nh:, 3], r[nh:, 4], r[nh:, 5], r[nh:, 6] = g.random(len(ri)) * (wh[ri, 0] - rw), g.random(len(ri)) * (wh[ri, 1] - rh), rw, rh
         r[:, 2] = np.floor(g.random(det_per_cat) * 4096) / 4096
     return gt, rows
+
+
+def synthetic_coco(n_img=5000, n_cat=80, gt_per_img=7.0, det_per_img=100, seed=0, crowd_frac=0.02, hit_frac=0.5, grid=0):
+    """Seeded COCO-shaped ground truth (a dict in COCO json format, `crowd_frac` of the annotations iscrowd) and predictions as the
+    engine holds them: [(image id, (width, height) of the network input, boxes xyxy float32 [n, 4] at that size, scores float32 [n],
+    labels int64 [n] = 1 + the category's position)], `det_per_img` per image.  A `hit_frac` share of an image's detections are jittered
+    copies of its ground truths (with their category most of the time), the rest are random.  Scores are quantised to 1/1024 so that ties
+    occur.  grid > 0: the network input has the image's size and every coordinate is a multiple of 1 / grid (exact in fp32 sums)."""
+    import numpy as np
+    g = np.random.default_rng(seed)
+    img_ids = np.sort(g.choice(np.arange(1, 600000), n_img, replace=False))
+    cat_ids = np.sort(g.choice(np.arange(1, 4 * n_cat + 1), n_cat, replace=False))
+    wh = g.integers(320, 641, (n_img, 2))
+    pwh = wh if grid else g.integers(400, 801, (n_img, 2))
+    ng = g.poisson(gt_per_img, n_img)
+    gi = np.repeat(np.arange(n_img), ng)
+    n_gt = len(gi)
+    gc = g.integers(0, n_cat, n_gt)
+    gw = np.maximum(g.random(n_gt) ** 2 * wh[gi, 0] * 0.8, 2.0)
+    gh = np.maximum(g.random(n_gt) ** 2 * wh[gi, 1] * 0.8, 2.0)
+    gx, gy = g.random(n_gt) * (wh[gi, 0] - gw), g.random(n_gt) * (wh[gi, 1] - gh)
+    if grid:
+        gx, gy, gw, gh = (np.round(v * grid) / grid for v in (gx, gy, np.maximum(gw, 2.0), np.maximum(gh, 2.0)))
+    crowd = g.random(n_gt) < crowd_frac
+    anns = [{"id": int(n + 1), "image_id": int(img_ids[gi[n]]), "category_id": int(cat_ids[gc[n]]), "iscrowd": int(crowd[n]),
+             "bbox": [float(gx[n]), float(gy[n]), float(gw[n]), float(gh[n])], "area": float(gw[n] * gh[n])} for n in range(n_gt)]
+    gt = {"images": [{"id": int(img_ids[i]), "width": int(wh[i, 0]), "height": int(wh[i, 1])} for i in range(n_img)], "annotations": anns,
+          "categories": [{"id": int(c), "name": f"c{c}"} for c in cat_ids]}
+    first = np.concatenate([[0], np.cumsum(ng)])
+    N = n_img * det_per_img
+    di = np.repeat(np.arange(n_img), det_per_img)
+    hit = (g.random(N) < hit_frac) & (ng[di] > 0)
+    src = np.minimum(first[di] + (g.random(N) * ng[di]).astype(np.int64), max(n_gt - 1, 0))
+    j = lambda v, s: v * (1 + s * g.standard_normal(N))                                   # noqa: E731
+    rw, rh = g.random(N) * wh[di, 0] * 0.5 + 2, g.random(N) * wh[di, 1] * 0.5 + 2
+    rx, ry = g.random(N) * (wh[di, 0] - rw), g.random(N) * (wh[di, 1] - rh)
+    if n_gt:
+        x, y = np.where(hit, j(gx[src] + 1, 0.05), rx), np.where(hit, j(gy[src] + 1, 0.05), ry)
+        w, h = np.where(hit, np.maximum(j(gw[src], 0.1), 1.0), rw), np.where(hit, np.maximum(j(gh[src], 0.1), 1.0), rh)
+        lab = np.where(hit & (g.random(N) < 0.8), gc[src], g.integers(0, n_cat, N)) + 1
+    else:
+        x, y, w, h, lab = rx, ry, rw, rh, g.integers(0, n_cat, N) + 1
+    if grid:
+        x, y, w, h = (np.round(v * grid) / grid for v in (x, y, np.maximum(w, 1.0), np.maximum(h, 1.0)))
+    sx, sy = pwh[di, 0] / wh[di, 0], pwh[di, 1] / wh[di, 1]
+    # xyxy with the legacy convention: convert("xywh") adds 1 to x2 - x1
+    boxes = np.stack([x * sx, y * sy, (x + w - 1) * sx, (y + h - 1) * sy], 1).astype(np.float32)
+    scores = (np.floor(g.random(N) * 1024) / 1024).astype(np.float32)
+    preds = []
+    for i in range(n_img):
+        s = slice(i * det_per_img, (i + 1) * det_per_img)
+        preds.append((int(img_ids[i]), (int(pwh[i, 0]), int(pwh[i, 1])), boxes[s], scores[s], lab[s].astype(np.int64)))
+    return gt, preds

@@ -1,0 +1,336 @@
+"""COCO AP (mq_det_amd.evaluation.CocoAPEvaluator, csrc/coco_eval.hip) without a GPU: the kernel SOURCES through the host emulation (tests/simt)
+against tests/golden/coco_eval_{bridge,small,medium} (tools/gen_golden_coco_eval.py).  `bridge` holds what the reference's own LVISEval gives
+on a ground truth where LVIS and COCO rules coincide -- that pins the restatement tests/coco_eval_ref.py, whose outputs are the expectation
+everywhere else (pycocotools is not installed where the fixtures are made; see that file's docstring).  One pair above the match kernel's
+fast-path limit against the restated evaluateImg; `update` against the reference's own prepare_for_coco_detection; the refusals."""
+import copy
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import coco_eval_ref as ref  # noqa: E402
+from mq_det_amd.evaluation import CocoAPEvaluator  # noqa: E402
+from mq_det_amd.structures import BoxList  # noqa: E402
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "coco_eval_")
+_CXX = os.environ.get("SIMT_CXX", "/opt/rocm/lib/llvm/bin/clang++")
+needs_simt = pytest.mark.skipif(not os.path.exists(_CXX), reason=f"{_CXX} not found: the kernel-source emulation cannot be built here")
+FAST_GT = 256                                   # csrc/coco_eval.hip COCO_FAST_GT
+
+
+def load_case(name):
+    with open(GOLD + name + ".json") as f:
+        js = json.load(f)
+    return js, dict(np.load(GOLD + name + ".npz"))
+
+
+def label_map(js):
+    return {int(k): int(v) for k, v in js["label_to_cat_id"]} if js.get("label_to_cat_id") else None
+
+
+def items_of(js, a):
+    """the fixture's predictions as the restatement takes them, in the order the generator fed them"""
+    return [(i, tuple(js["sizes"][str(i)]), a["boxes"][a["image_id"] == i], a["scores"][a["image_id"] == i], a["labels"][a["image_id"] == i])
+            for i in js["image_order"]]
+
+
+def boxlist(item, device="cpu"):
+    i, size, boxes, scores, labels = item
+    bl = BoxList(torch.from_numpy(np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)).to(device), size, "xyxy")
+    bl.add_field("scores", torch.from_numpy(np.ascontiguousarray(scores, np.float32)).to(device))
+    bl.add_field("labels", torch.from_numpy(np.ascontiguousarray(labels, np.int64)).to(device))
+    return i, bl
+
+
+def feed(ev, items, device="cpu"):
+    """the engine's calls: first a prediction that a later one replaces, update with three images at a time (a dict and a list of pairs in
+    turn), then one image once more"""
+    preds = [boxlist(it, device) for it in items]
+    full = [p for p in preds if len(p[1])]
+    if len(full) > 1:
+        ev.update({full[-1][0]: full[0][1]})                       # another image's boxes under the last image's id: replaced below
+    for n in range(0, len(preds), 3):
+        ev.update(dict(preds[n:n + 3]) if n % 2 else preds[n:n + 3])
+    if full:
+        ev.update([full[0]])                                       # the duplicated image
+
+
+def run_case(js, a, device="cpu"):
+    ev = CocoAPEvaluator(js["gt"], device=device, label_to_cat_id=label_map(js))
+    feed(ev, items_of(js, a), device)
+    ev.synchronize_between_processes()
+    strings = ev.summarize()
+    return ev, strings
+
+
+def pairs_of(ev):
+    """-> (pair image ids, pair category ids, detections per pair, dt_bits as uint64, gt_count) from the match kernel's outputs"""
+    e, K = ev.eval, ev.K
+    img, cat = ev.img_ids_f.cpu().long().numpy(), ev.cat_ids_f.cpu().long().numpy()
+    pk = e["pair_key"].cpu().numpy()
+    return (img[pk // K], cat[pk % K], e["pair_dt"][:, 1].cpu().numpy(), e["dt_bits"].cpu().numpy().view(np.uint64),
+            e["gt_count"].cpu().numpy())
+
+
+def check_case(js, a, ev, strings):
+    assert np.array_equal(ev.eval["precision"].cpu().numpy(), a["precision"])
+    assert np.array_equal(ev.eval["recall"].cpu().numpy(), a["recall"])
+    pi, pc, pd, pb, cnt = pairs_of(ev)
+    assert np.array_equal(pi, a["pair_img"]) and np.array_equal(pc, a["pair_cat"]) and np.array_equal(pd, a["pair_D"])
+    assert np.array_equal(pb, a["dt_bits"]) and np.array_equal(cnt, a["gt_count"])
+    assert len(ev.stats) == 12 and all(type(v) is float for v in ev.stats)
+    for got, want in zip(ev.stats, js["stats"]):
+        assert abs(got - want) <= 1e-12, (got, want)
+    assert list(ev.results) == ["bbox"] and list(ev.results["bbox"]) == list(js["results"]["bbox"])
+    for k, v in js["results"]["bbox"].items():
+        assert abs(ev.results["bbox"][k] - v) <= 1e-12, (k, ev.results["bbox"][k], v)
+    assert strings == js["strings"]
+    assert "".join(ev.per_category()) == js["per_category"]
+
+
+@pytest.fixture(scope="module")
+def emu():
+    import simt
+    with simt.installed() as ops:
+        yield ops
+
+
+def test_small_fixture_covers_every_rule():
+    """the hand-made fixture reaches what it is meant to, before anything is compared with it"""
+    js, a = load_case("small")
+    gt, rows = js["gt"], a["rows"]
+    img_ids, cat_ids, gts, dts = ref.prepare(gt, rows)
+    E = {(i, c): [ref.evaluate_img(dts.get((i, c), []), gts.get((i, c), []), rng, ids=True) for rng in ref.AREA_RNG]
+         for (i, c) in set(gts) | set(dts)}
+    crowd_twice = crowd_beaten = inside = once_only = unmatched_out = half = three_quarters = False
+    for (i, c), per_area in E.items():
+        G = gts.get((i, c), [])
+        for ai, (dtm, dt_ig, gt_ig, sc, D) in enumerate(per_area):
+            lo, hi = ref.AREA_RNG[ai]
+            unmatched_out |= any(dtm[0, d] == 0 and (D[d][2] < lo or D[d][2] > hi) and dt_ig[0, d] for d in range(len(D)))
+            for g in G:
+                hits = [d for d in range(len(D)) if dtm[0, d] == g[0] and g[0] != 0]
+                if g[3]:
+                    crowd_twice |= len(hits) >= 2
+                    inside |= any(ref.bbiou(D[d][1], g[1], True) == 1.0 and D[d][2] < g[2] for d in hits)
+                elif g[2] < lo or g[2] > hi:
+                    once_only |= len(hits) == 1 and sum(ref.bbiou(d[1], g[1], False) >= 0.5 for d in D) >= 2
+                else:
+                    for d in hits:
+                        crowd_beaten |= any(k[3] and ref.bbiou(D[d][1], k[1], True) > ref.bbiou(D[d][1], g[1], False) for k in G)
+        for d in dts.get((i, c), []):
+            half |= any(ref.bbiou(d[1], g[1], False) == 0.5 for g in G if not g[3])
+            three_quarters |= any(ref.bbiou(d[1], g[1], False) == 0.75 for g in G if not g[3])
+    assert crowd_twice and crowd_beaten and inside and once_only and unmatched_out and half and three_quarters
+    assert any(x["id"] == 0 for x in gt["annotations"]) and any(x.get("iscrowd") for x in gt["annotations"])
+    assert any("iscrowd" not in x for x in gt["annotations"])
+    assert any(len({d[0] for d in v}) < len(v) for v in dts.values())                                      # a score tie inside a pair
+    by_cat = {}
+    for (i, c), v in dts.items():
+        for d in v:
+            by_cat.setdefault((c, d[0]), set()).add(i)
+    assert any(len(v) > 1 for v in by_cat.values())                                                        # ... and one across images
+    assert max(len(v) for v in dts.values()) > 100
+    gt_cats, dt_cats = {c for _, c in gts}, {c for _, c in dts}
+    assert (gt_cats - dt_cats) and (dt_cats - gt_cats)
+    assert set(img_ids) - {i for i, _ in gts} - {i for i, _ in dts}                                        # an image with neither
+    assert set(rows[:, 1].astype(int)) - set(cat_ids)                                                      # a category the file lacks
+    assert any(x["category_id"] not in cat_ids for x in gt["annotations"]) and any(x["image_id"] not in img_ids for x in gt["annotations"])
+    assert set(a["labels"].tolist()) - set(label_map(js))                                                  # an unknown label
+    assert any((a["image_id"] == i).sum() == 0 for i in js["image_order"])                                 # an empty prediction
+    p = a["precision"]
+    assert (p == -1).any() and (p == 0).any() and (p > 0).any()
+    assert js["stats"][6] < js["stats"][7] < js["stats"][8]                                                # AR@1 < AR@10 < AR@100
+
+
+def test_restatement_reproduces_the_reference_on_the_bridge():
+    """tests/coco_eval_ref.py on the bridge rows = the reference's own LVISEval: precision and recall at maxDets 100, every pair's flags"""
+    js, a = load_case("bridge")
+    assert not any(x.get("iscrowd") or x.get("ignore") for x in js["gt"]["annotations"])
+    rows = ref.result_rows(items_of(js, a), js["gt"], label_map(js))
+    assert np.array_equal(rows, a["rows"]) and np.unique(rows[:, :2], axis=0, return_counts=True)[1].max() <= 100
+    out = ref.evaluate(js["gt"], rows)
+    assert np.array_equal(out["precision"][..., 2], a["lvis_precision"]) and np.array_equal(out["recall"][..., 2], a["lvis_recall"])
+    assert (a["lvis_precision"] > 0).any()
+    got = ref.pack_bits(out["flags"], out["img_ids"], out["cat_ids"])
+    for k, v in zip(("pair_img", "pair_cat", "pair_D", "dt_bits", "gt_count"), got):
+        assert np.array_equal(v, a["lvis_" + k]), k
+    assert np.array_equal(out["precision"], a["precision"]) and np.array_equal(out["recall"], a["recall"])
+
+
+@pytest.mark.parametrize("name", ["small", "medium"])
+def test_restatement_reproduces_its_fixtures(name):
+    js, a = load_case(name)
+    rows = ref.result_rows(items_of(js, a), js["gt"], label_map(js))
+    out = ref.evaluate(js["gt"], rows)
+    assert np.array_equal(rows, a["rows"]) and np.array_equal(out["precision"], a["precision"]) and np.array_equal(out["recall"], a["recall"])
+    assert out["strings"] == js["strings"]
+
+
+@needs_simt
+@pytest.mark.parametrize("name", ["bridge", "small", "medium"])
+def test_fixture_is_exact(emu, name):
+    js, a = load_case(name)
+    ev, strings = run_case(js, a)
+    check_case(js, a, ev, strings)
+    if name == "bridge":
+        assert np.array_equal(ev.eval["precision"][..., 2].numpy(), a["lvis_precision"])
+        assert np.array_equal(ev.eval["recall"][..., 2].numpy(), a["lvis_recall"])
+        assert np.array_equal(pairs_of(ev)[3], a["lvis_dt_bits"])
+
+
+def big_pair(seed=3, n_dt=140, n_gt=300):
+    """one image, one category: more ground truths than the match kernel's fast path holds, crowds among them, more than 100 detections"""
+    g = np.random.default_rng(seed)
+    gx, gy = g.random(n_gt) * 900, g.random(n_gt) * 900
+    gw = g.choice([8.0, 20.0, 40.0, 90.0, 150.0], n_gt) * (0.8 + 0.4 * g.random(n_gt))
+    gh = g.choice([8.0, 20.0, 40.0, 90.0], n_gt) * (0.8 + 0.4 * g.random(n_gt))
+    anns = [{"id": n + 1, "image_id": 7, "category_id": 3, "bbox": [float(gx[n]), float(gy[n]), float(gw[n]), float(gh[n])],
+             "area": float(gw[n] * gh[n]), "iscrowd": int(n % 11 == 0)} for n in range(n_gt)]
+    gt = {"images": [{"id": 7, "width": 1100, "height": 1100}], "annotations": anns, "categories": [{"id": 3, "name": "c3"}]}
+    src = g.integers(0, n_gt, n_dt)
+    x = gx[src] + g.standard_normal(n_dt) * gw[src] * 0.1
+    y = gy[src] + g.standard_normal(n_dt) * gh[src] * 0.1
+    w = gw[src] * (1 + 0.15 * g.standard_normal(n_dt))
+    h = gh[src] * (1 + 0.15 * g.standard_normal(n_dt))
+    boxes = np.stack([x, y, x + w - 1, y + h - 1], 1).astype(np.float32)
+    s = (np.floor(g.random(n_dt) * 64) / 64).astype(np.float32)
+    return gt, [(7, (1100, 1100), boxes, s, np.ones(n_dt, np.int64))]
+
+
+def check_big_pair(device):
+    gt, items = big_pair()
+    ev = CocoAPEvaluator(gt, device=device)
+    ev.update([boxlist(items[0], device)])
+    ev.summarize()
+    assert ev.eval["pair_gt"][0, 1].item() > FAST_GT and ev.eval["pair_dt"][0, 1].item() == 100
+    rows = ref.result_rows(items, gt)
+    _, _, gts, dts = ref.prepare(gt, rows)
+    bits = pairs_of(ev)[3]
+    sh = np.arange(40, dtype=np.uint64)
+    m = ((bits[:, 0:1] >> sh) & np.uint64(1)).astype(bool).T.reshape(4, 10, -1)
+    ig = ((bits[:, 1:2] >> sh) & np.uint64(1)).astype(bool).T.reshape(4, 10, -1)
+    for ai, rng in enumerate(ref.AREA_RNG):
+        wm, wi, gig, _ = ref.evaluate_img(dts[(7, 3)], gts[(7, 3)], rng)
+        assert np.array_equal(m[ai], wm) and np.array_equal(ig[ai], wi), ai
+        assert ev.eval["gt_count"][0, ai].item() == int(np.count_nonzero(gig == 0))
+    assert m.any() and ig.any()
+    out = ref.evaluate(gt, rows)
+    assert np.array_equal(ev.eval["precision"].cpu().numpy(), out["precision"]) and np.array_equal(ev.eval["recall"].cpu().numpy(), out["recall"])
+
+
+@needs_simt
+def test_one_pair_above_the_fast_path_matches_the_restated_evaluate_img(emu):
+    check_big_pair("cpu")
+
+
+def check_random_case(device, n_img, n_cat, seed=2):
+    """a seeded random case (crowds, ties, non-square resizes) against the restatement"""
+    from mq_det_amd.utils.synth import synthetic_coco
+    gt, items = synthetic_coco(n_img=n_img, n_cat=n_cat, gt_per_img=6.0, det_per_img=50, seed=seed, crowd_frac=0.05)
+    ev = CocoAPEvaluator(gt, device=device)
+    feed(ev, items, device)
+    ev.synchronize_between_processes()
+    strings = ev.summarize()
+    out = ref.evaluate(gt, ref.result_rows(items, gt))
+    assert np.array_equal(ev.eval["precision"].cpu().numpy(), out["precision"]) and np.array_equal(ev.eval["recall"].cpu().numpy(), out["recall"])
+    got, want = pairs_of(ev), ref.pack_bits(out["flags"], out["img_ids"], out["cat_ids"])
+    for g_, w_ in zip(got, want):
+        assert np.array_equal(g_, w_)
+    assert strings == out["strings"] and all(abs(x - y) <= 1e-12 for x, y in zip(ev.stats, out["stats"]))
+    assert (out["precision"] > 0).any()
+    return ev
+
+
+def test_prepare_matches_the_reference():
+    """update = the reference's own prepare_for_coco_detection (BoxList.resize + convert("xywh") + the label map), bit for bit; the per-category
+    lines = the reference's summarize_per_category on the fixture's stub"""
+    js, a = load_case("prepare")
+    items = items_of(js, a)
+    ev = CocoAPEvaluator(js["gt"], device="cpu", label_to_cat_id=label_map(js))
+    ev.update([boxlist(it) for it in items])
+    ev.acc._fold()
+    rows = ev.acc.rows
+    assert rows.shape[1] == 8 and int(rows[:, 7].sum()) == len(items)
+    unknown = set(a["labels"].tolist()) - set(label_map(js))
+    assert unknown and int(torch.isnan(rows[:, 1]).sum()) == int(np.isin(a["labels"], list(unknown)).sum()) + 1      # + the empty prediction
+    kept = rows[~torch.isnan(rows[:, 1])][:, :7].double().numpy()
+    assert np.array_equal(kept, a["rows"])                                                                          # boxes bit-equal, labels mapped
+    assert set(kept[:, 1].astype(int)) <= set(label_map(js).values())
+    ev.eval = {"precision": torch.from_numpy(a["precision"])}
+    assert "".join(ev.per_category()) == js["per_category"]
+    assert [round(v, 12) for v in js["results"]["bbox"].values()] == [round(float(v), 12) for v in a["stats"][:6]]
+
+
+def test_per_category_writes_the_csv(tmp_path):
+    js, a = load_case("prepare")
+    ev = CocoAPEvaluator(js["gt"], device="cpu")
+    ev.eval = {"precision": torch.from_numpy(a["precision"])}
+    lines = ev.per_category(str(tmp_path / "bbox.csv"))
+    assert (tmp_path / "bbox.csv").read_text() == js["per_category"] == "".join(lines) and len(lines) == 6
+
+
+@pytest.mark.parametrize("field", ["images.id", "categories.id", "annotations.image_id", "annotations.category_id"])
+def test_ids_the_fp32_rows_cannot_hold_are_refused(field):
+    js, _ = load_case("small")
+    gt = copy.deepcopy(js["gt"])
+    big = (1 << 24) + 1
+    if field == "images.id":
+        gt["images"][0]["id"] = big
+    elif field == "categories.id":
+        gt["categories"][0]["id"] = big
+    else:
+        gt["annotations"][0][field.split(".")[1]] = big
+    with pytest.raises(ValueError, match=field.replace(".", r"\.")):
+        CocoAPEvaluator(gt, device="cpu")
+
+
+def test_other_refusals_at_construction_and_update():
+    js, a = load_case("small")
+    gt = copy.deepcopy(js["gt"])
+    gt["images"][0]["id"] = 10.5
+    with pytest.raises(ValueError, match=r"images\.id"):
+        CocoAPEvaluator(gt, device="cpu")
+    gt = copy.deepcopy(js["gt"])
+    gt["annotations"][1]["id"] = gt["annotations"][0]["id"]
+    with pytest.raises(ValueError, match=r"annotations\.id"):
+        CocoAPEvaluator(gt, device="cpu")
+    ev = CocoAPEvaluator(js["gt"], device="cpu")
+    with pytest.raises(ValueError, match=r"predictions\.image_id"):
+        ev.update([((1 << 24) + 1, boxlist(items_of(js, a)[0])[1])])
+
+
+@needs_simt
+def test_an_image_the_ground_truth_lacks_is_refused_at_summarize(emu):
+    js, a = load_case("small")
+    ev = CocoAPEvaluator(js["gt"], device="cpu", label_to_cat_id=label_map(js))
+    items = items_of(js, a)
+    feed(ev, items)
+    ev.update([(77, boxlist(items[0])[1])])
+    with pytest.raises(ValueError, match="image ids"):
+        ev.summarize()
+    ev = CocoAPEvaluator(js["gt"], device="cpu", label_to_cat_id=label_map(js))
+    feed(ev, items)
+    ev.update([(77, boxlist((77, (10, 10), np.zeros((0, 4)), np.zeros(0), np.zeros(0)))[1])])          # empty: nothing reaches the results
+    assert ev.summarize() == js["strings"]
+
+
+def test_gt_from_a_path_and_a_coco_like_object(tmp_path):
+    js, _ = load_case("small")
+    p = tmp_path / "gt.json"
+    p.write_text(json.dumps(js["gt"]))
+    obj = type("COCO", (), {"dataset": js["gt"]})()
+    a, b = CocoAPEvaluator(str(p), device="cpu"), CocoAPEvaluator(obj, device="cpu")
+    assert torch.equal(a.gt_box, b.gt_box) and torch.equal(a.gt_key, b.gt_key) and torch.equal(a.gt_crowd, b.gt_crowd)
+    assert a.lbl_keys.tolist() == list(range(1, a.K + 1)) and a.lbl_vals.tolist() == [float(c) for c in a.cat_ids]
+
+
+@needs_simt
+def test_random_case_matches_the_restatement(emu):
+    check_random_case("cpu", 40, 6)
