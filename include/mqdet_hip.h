@@ -505,6 +505,20 @@ int mq_coco_match(const int* pair_dt, const int* pair_gt, const float* dt_box, c
 int mq_coco_accumulate(const int* cat_off, const int* order, const int* rank, const unsigned long long* dt_bits, const int* num_gt,
                        const int* max_dets, const double* rec_thr, double* precision, double* recall, int K, void* stream);
 
+/* ---- Flickr30k Entities Recall@k (csrc/flickr_eval.hip, host side mq_det_amd/evaluation.py FlickrRecallEvaluator).  fp64 / fp32 / integer data only.
+ * mq_flickr_recall: one wave per phrase.  phrase_dt / phrase_gt [P, 2] int32 = (first, count) of the phrase's detections (dt_box [*, 4] fp32 xyxy,
+ *   score descending; the dummy box [0, 0, 0, 0] of flickr_post_process is implied behind them and counts towards k) and ground truths (gt_box
+ *   [*, 4] fp64 xyxy); ks [NK] int32, NK <= 30, every k > 0 or -1 = all; iou_thr [1] fp64 = the IoU threshold.
+ *   -> hits [P] int32: bit j = `box_iou(pred, gt)[:ks[j]].max() >= iou_thr[0]` in fp64 without contraction (area without + 1); a NaN among those
+ *   IoUs is a miss, like numpy's max.
+ * mq_flickr_tally: cat_off [P + 1] / cat_idx [*] int32 = CSR of every phrase's category columns in 1 .. C - 1 (column 0, "all", is implied)
+ *   -> positives [NK, C] and totals [C] uint64, ADDED to what the buffers hold (zero them first), integer atomics.
+ * Replaces flickr_eval.py:152-202,220-255,362-380 (box_iou, RecallTracker, the phrase loop of Flickr30kEntitiesRecallEvaluator.evaluate). */
+int mq_flickr_recall(const int* phrase_dt, const int* phrase_gt, const float* dt_box, const double* gt_box, const int* ks, const double* iou_thr,
+                     int* hits, int P, int NK, void* stream);
+int mq_flickr_tally(const int* hits, const int* cat_off, const int* cat_idx, unsigned long long* positives, unsigned long long* totals, int P,
+                    int NK, int C, void* stream);
+
 /* ---- Vision-query bank (csrc/query_bank.hip, host side mq_det_amd/query_bank.py QueryBank).  fp32 / integer data only.
  * The admission loop of generalized_vl_rcnn_new.py:269-287 (== groundingdino.py:401-421) for N candidates in one launch.  cand [N, D] fp32
  * (D = scales x channels); sorted_labels / order [N] int64 = the candidates' labels after ONE stable sort and the sort's permutation; workgroup b

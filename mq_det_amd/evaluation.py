@@ -16,10 +16,13 @@ exchanges them between ranks by pickling the whole dict through two all_gathers 
 Image ids must be exactly representable in fp32 (< 2^24; LVIS / COCO ids are < 600 000).
 
 `LvisFixedAPEvaluator` computes the LVIS Fixed AP from that state on the device (csrc/lvis_eval.hip; DESIGN.md "LVIS Fixed AP").
-`CocoAPEvaluator` computes pycocotools' COCO AP (COCO / ODinW) from rows of the same kind (csrc/coco_eval.hip; DESIGN.md "COCO AP")."""
+`CocoAPEvaluator` computes pycocotools' COCO AP (COCO / ODinW) from rows of the same kind (csrc/coco_eval.hip; DESIGN.md "COCO AP").
+`FlickrRecallEvaluator` computes Flickr30k Entities Recall@k (phrase grounding) from such rows (csrc/flickr_eval.hip; DESIGN.md "Phrase grounding")."""
 import json
 import math
 import os
+import re
+import warnings
 from collections import OrderedDict, defaultdict
 
 import numpy as np
@@ -604,3 +607,269 @@ class CocoAPEvaluator:
                 for text in out:
                     f.writelines(text)
         return out
+
+
+# ====================================================================================================== Flickr30k Entities Recall@k on the device
+_FLICKR_PHRASE = re.compile(r"\[/EN#([^/\s\]]+)((?:/[^/\s\]]*)*)\s")
+
+
+def read_entities_sentences(path):
+    """One `Sentences/<image>.txt` of Flickr30k Entities: a caption per non-empty line, an annotated phrase written `[/EN#<id>/<type>/<type> words]`
+    (zero or more types) -> per caption the list of {"phrase_id", "phrase_type": [...]} in reading order."""
+    with open(path) as f:
+        lines = [ln for ln in f.read().split("\n") if ln.strip()]
+    return [[{"phrase_id": m.group(1), "phrase_type": [t for t in m.group(2).split("/")[1:]]} for m in _FLICKR_PHRASE.finditer(ln + " ")]
+            for ln in lines]
+
+
+def read_entities_boxes(path):
+    """One `Annotations/<image>.xml` of Flickr30k Entities: every <object> names one or more phrase ids (<name>) and either carries a <bndbox>
+    (xmin, ymin, xmax, ymax) or a <nobndbox> / <scene> mark -> {phrase id: [[x1, y1, x2, y2], ...]} of the ids with boxes, in file order."""
+    import xml.etree.ElementTree as ET
+    boxes = {}
+    for obj in ET.parse(path).getroot().iter("object"):
+        bb = obj.find("bndbox")
+        if bb is None:
+            continue
+        box = [int(bb.findtext(tag)) for tag in ("xmin", "ymin", "xmax", "ymax")]
+        for name in obj.findall("name"):
+            boxes.setdefault(name.text, []).append(list(box))
+    return boxes
+
+
+class FlickrRecallEvaluator:
+    """The phrase-grounding branch of the reference's engine/inference.py (`TEST.EVAL_TASK = "grounding"`: `flickr_post_process` :322-338, the
+    evaluator calls :701-724) and data/datasets/evaluation/flickr/flickr_eval.py (`FlickrEvaluator`, `Flickr30kEntitiesRecallEvaluator`,
+    `RecallTracker`) with the detections kept as fp32 device rows.  `update_boxlist` is resize_box + flickr_post_process without a host sync,
+    `update` takes the reference's post-processed dicts, `synchronize_between_processes` is `FixedAPAccumulator`'s fixed-shape exchange,
+    `summarize()` groups with torch sorts, runs csrc/flickr_eval.hip and returns the reference's `score` dict after one host sync.
+
+    gt: {image id: [sentence, ...]}, a sentence being a list of phrases {"phrase_id", "phrase_type": [...]} or None (not evaluated);
+    boxes: {image id: {phrase id: [[x1, y1, x2, y2], ...]}}.  Phrases without boxes are dropped and a sentence that keeps none is not
+    evaluated, as in flickr_eval.py:305-318.  Rows [n, 8] fp32: a prediction is one header row (sentence slot, number of phrase lists, -1,
+    0.., mark 1) followed by its detections (sentence slot, phrase, score, x1, y1, x2, y2, mark 0); the running sum of the marks is the
+    arrival number, also after the gather.
+
+    Rules (flickr_eval.py:323-390): the first prediction of a sentence wins, later ones are dropped with a warning; predictions for a
+    sentence that is not evaluated are ignored; a wrong number of phrase lists, a phrase index outside the sentence, a missing prediction
+    raise RuntimeError in `summarize()`.  An unknown image id or a sentence id outside the image's list raises RuntimeError in `update*`
+    (the reference's two checks of that kind come after its `all_ids` filter and are never reached; here they are).  Within a phrase the
+    order is score descending, ties in detection order (`torch.topk` leaves the order of ties open)."""
+
+    def __init__(self, gt, boxes=None, topk=(1, 5, 10, -1), iou_thresh=0.5, merge_boxes=False, device="cuda"):
+        if boxes is None:
+            gt, boxes = gt
+        self.device = torch.device(device)
+        self.topk = tuple(int(k) for k in topk)
+        if not self.topk or len(self.topk) > 30 or any(k == 0 or k < -1 for k in self.topk):
+            raise ValueError("topk: 1 to 30 values, each > 0 or -1 (all)")
+        self.iou_thresh = float(iou_thresh)
+        self.acc = _ResultRows(self.device)
+        self.results = None
+        self.eval = {}
+        self._ingest(gt, boxes, merge_boxes)
+
+    @classmethod
+    def from_entities_dir(cls, path, subset="test", merge_boxes=False, **kw):
+        """The Flickr30k Entities layout: `<subset>.txt` (an image id per line), `Annotations/<id>.xml`, `Sentences/<id>.txt`."""
+        with open(os.path.join(path, f"{subset}.txt")) as f:
+            ids = [ln.strip() for ln in f]
+        gt = OrderedDict((i, read_entities_sentences(os.path.join(path, "Sentences", f"{i}.txt"))) for i in ids)
+        boxes = {i: read_entities_boxes(os.path.join(path, "Annotations", f"{i}.xml")) for i in ids}
+        return cls(gt, boxes, merge_boxes=merge_boxes, **kw)
+
+    # ------------------------------------------------------------------ ground truth, once
+    def _ingest(self, gt, boxes, merge_boxes):
+        dev = self.device
+        self.sentences, self.gt_boxes = OrderedDict(), {}
+        self.slot = {}                                           # (image id, sentence id) -> slot of an evaluated sentence
+        self.slot_name = []
+        ph_off, phrase_gt, gt_box, cat_off, cat_idx = [0], [], [], [0], []
+        boxes = {str(k): v for k, v in boxes.items()}
+        kept_types = set()
+        for img, sents in gt.items():
+            img = str(img)
+            bx = {}
+            for pid, bl in boxes.get(img, {}).items():
+                b = np.asarray(bl, dtype=np.float64).reshape(-1, 4)
+                if merge_boxes and len(b) > 1:
+                    b = np.array([[b[:, 0].min(), b[:, 1].min(), b[:, 2].max(), b[:, 3].max()]])
+                bx[str(pid)] = b
+            self.gt_boxes[img] = {k: v.tolist() for k, v in bx.items()}
+            out = []
+            for s in sents:
+                kept = [{"phrase_id": str(p["phrase_id"]), "phrase_type": list(p["phrase_type"])} for p in (s or []) if str(p["phrase_id"]) in bx]
+                out.append(kept if kept else None)
+                for p in kept:
+                    kept_types.update(p["phrase_type"])
+            self.sentences[img] = out
+        self.categories = ["all"] + sorted(kept_types - {"all"})
+        col = {c: n for n, c in enumerate(self.categories)}
+        for img, sents in self.sentences.items():
+            for sid, s in enumerate(sents):
+                if s is None:
+                    continue
+                self.slot[(img, sid)] = len(self.slot_name)
+                self.slot_name.append((img, sid))
+                for p in s:
+                    b = np.asarray(self.gt_boxes[img][p["phrase_id"]], dtype=np.float64).reshape(-1, 4)
+                    phrase_gt.append((len(gt_box), len(b)))
+                    gt_box.extend(b.tolist())
+                    cat_idx.extend(col[t] for t in p["phrase_type"])
+                    cat_off.append(len(cat_idx))
+                ph_off.append(len(phrase_gt))
+        if len(self.slot_name) >= _ID_LIMIT:
+            raise ValueError("more than 2^24 evaluated sentences (the rows keep the sentence slot as fp32)")
+        t = lambda a, dt, shape: torch.tensor(a, dtype=dt).reshape(shape).to(dev)          # noqa: E731
+        self.S, self.P = len(self.slot_name), len(phrase_gt)
+        self.ph_off = t(ph_off, torch.int64, (-1,))
+        self.phrase_gt = t(phrase_gt, torch.int32, (-1, 2)).contiguous()
+        self.gt_box = t(gt_box, torch.float64, (-1, 4)).contiguous()
+        self.cat_off = t(cat_off, torch.int32, (-1,))
+        self.cat_idx = t(cat_idx, torch.int32, (-1,))
+        self.ks = t(list(self.topk), torch.int32, (-1,))
+        self.iou_thr_t = t([self.iou_thresh], torch.float64, (-1,))
+
+    # ------------------------------------------------------------------ the engine's calls
+    def _slot_of(self, image_id, sentence_id):
+        """-> slot, or None for a sentence that is not evaluated; RuntimeError for ids the ground truth does not hold"""
+        img = str(int(image_id)) if torch.is_tensor(image_id) else str(image_id)
+        if img not in self.sentences:
+            raise RuntimeError(f"Unknown image id {img}")
+        sid = int(sentence_id)
+        if not 0 <= sid < len(self.sentences[img]):
+            raise RuntimeError(f"Unknown sentence id {sid} in image {img}")
+        return self.slot.get((img, sid))
+
+    def _header(self, slot, n_lists, n_rows):
+        r = torch.zeros(1 + n_rows, 8, dtype=torch.float32, device=self.device)
+        r[:, 0] = float(slot)
+        r[0, 1], r[0, 2], r[0, 7] = float(n_lists), -1.0, 1.0
+        return r
+
+    def update(self, predictions):
+        """predictions: the reference's `mdetr_style_output`, [{"image_id", "sentence_id", "boxes": per phrase a list of [x1, y1, x2, y2] in
+        the order to evaluate them (flickr_post_process: score descending, the dummy box last), "scores"}] -- `FlickrEvaluator.update`.  The
+        lists' own order is kept (the rows' score is minus the position); the dummy box the kernel implies behind every list repeats the
+        one the list ends with, which changes no prefix maximum."""
+        for pred in predictions:
+            slot = self._slot_of(pred["image_id"], pred["sentence_id"])
+            if slot is None:
+                if any(len(b) for b in pred["boxes"]):
+                    warnings.warn(f"in image {pred['image_id']} no predictions were expected for sentence {pred['sentence_id']}: ignored")
+                continue
+            lists = [np.asarray(b, dtype=np.float64).reshape(-1, 4) for b in pred["boxes"]]
+            n = sum(len(b) for b in lists)
+            if len(lists) >= _ID_LIMIT:
+                raise ValueError("more than 2^24 phrase lists in one prediction")
+            r = self._header(slot, len(lists), n)
+            if n:
+                body = np.zeros((n, 6), dtype=np.float32)
+                body[:, 0] = np.concatenate([np.full(len(b), j) for j, b in enumerate(lists)])
+                body[:, 1] = np.concatenate([-np.arange(len(b)) for b in lists])
+                body[:, 2:] = np.concatenate(lists)
+                r[1:, 1:7] = torch.from_numpy(body).to(self.device)
+            self.acc.append(r)
+
+    def update_boxlist(self, image_id, sentence_id, boxlist, n_phrases, plus=0, orig_size=None):
+        """One raw output of the model -> rows, on the device and without a host sync: `resize_box` (to orig_size = (height, width), host
+        numbers or a host tensor; None = keep the size) and `flickr_post_process` (phrase = label - plus; the per-phrase lists and their order
+        are made in `summarize()`)."""
+        slot = self._slot_of(image_id, sentence_id)
+        if slot is None:
+            return
+        bl = boxlist.to(self.device)
+        if orig_size is not None:
+            h, w = (float(v) for v in orig_size)
+            bl = bl.resize((w, h))
+        n = len(bl)
+        r = self._header(slot, int(n_phrases), n)
+        if n:
+            r[1:, 1] = (bl.get_field("labels").to(self.device) - int(plus)).float()
+            r[1:, 2] = bl.get_field("scores").to(self.device).float()
+            r[1:, 3:7] = bl.convert("xyxy").bbox.float()
+        self.acc.append(r)
+
+    def accumulate(self):
+        pass
+
+    def synchronize_between_processes(self, group=None, force=False):
+        self.acc.synchronize_between_processes(group, force)
+
+    # ------------------------------------------------------------------ evaluate
+    def evaluate(self):
+        """-> (positives [K, C] int64, totals [C] int64, flags [4] int64: predictions dropped as duplicates, evaluated sentences without a
+        prediction, winners with a wrong number of phrase lists, detections with a phrase index outside their sentence) on the device;
+        the per-phrase hit bits are kept in self.eval (test hook)."""
+        from . import ops
+        acc, dev, S = self.acc, self.device, self.S
+        acc._fold()
+        rows = acc.rows
+        n = len(rows)
+        i64 = lambda *v: torch.tensor(v, dtype=torch.int64, device=dev)                   # noqa: E731
+        head = rows[:, 7] > 0
+        slot = rows[:, 0].long().clamp(0, max(S - 1, 0))
+        pred_no = torch.cumsum(head.long(), 0)                   # arrival number of the prediction a row belongs to, from 1
+        big = torch.full((), n + 1, dtype=torch.int64, device=dev)
+        first = torch.full((max(S, 1),), n + 1, dtype=torch.int64, device=dev)
+        first.scatter_reduce_(0, slot, torch.where(head, pred_no, big), "amin", include_self=True)
+        win = pred_no == first[slot]
+        dropped = (head & ~win).sum()
+        missing = (first[:S] > n).sum()
+        want = self.ph_off[1:] - self.ph_off[:-1]                # phrases per slot
+        bad_len = (head & win & (rows[:, 1].long() != want[slot])).sum() if S else i64(0)[0]
+        det = ~head & win
+        ph = rows[:, 1].long()
+        inside = (ph >= 0) & (ph < want[slot]) if S else det
+        bad_phrase = (det & ~inside).sum()
+        det &= inside
+        d = rows[det]
+        gp = (self.ph_off[:-1][slot[det]] + ph[det]) if S else ph[det]
+        o = torch.sort(d[:, 2], descending=True, stable=True)[1]                          # ties: detection order
+        o = o[torch.sort(gp[o], stable=True)[1]]
+        d, gp = d[o], gp[o]
+        pid = torch.arange(self.P, device=dev)
+        ds = torch.searchsorted(gp, pid)
+        de = torch.searchsorted(gp, pid, right=True)
+        phrase_dt = torch.stack([ds, de - ds], 1).to(torch.int32).contiguous()
+        dt_box = d[:, 3:7].contiguous()
+        hits = ops.flickr_recall(phrase_dt, self.phrase_gt, dt_box, self.gt_box, self.ks, self.iou_thr_t)
+        positives, totals = ops.flickr_tally(hits, self.cat_off, self.cat_idx, len(self.topk), len(self.categories))
+        flags = torch.stack([dropped, missing, bad_len, bad_phrase])
+        self.eval = {"hits": hits, "phrase_dt": phrase_dt, "dt_box": dt_box, "positives": positives, "totals": totals, "flags": flags,
+                     "first": first}
+        return positives, totals, flags
+
+    def summarize(self):
+        """FlickrEvaluator.summarize's `score`: {"Recall@1_all": .., .., "Upper_bound_<type>": ..}, k in topk order, categories sorted, values
+        positives / total as Python floats -- on every rank (after the exchange every rank holds all rows)."""
+        positives, totals, flags = self.evaluate()
+        K, C = positives.shape
+        vals = torch.cat([positives.reshape(-1), totals, flags]).cpu().tolist()           # the one host sync
+        pos, tot, (dropped, missing, bad_len, bad_phrase) = vals[:K * C], vals[K * C:K * C + C], vals[K * C + C:]
+        if dropped:
+            warnings.warn(f"multiple predictions found for {dropped} sentence prediction(s): the first one of a sentence counts")
+        if bad_len or bad_phrase:
+            raise RuntimeError(f"Error, {bad_len} prediction(s) with a number of phrase lists other than the sentence's number of phrases, "
+                               f"{bad_phrase} detection(s) with a phrase index outside their sentence")
+        if missing:
+            first = self.eval["first"][:self.S].cpu().tolist()
+            lost = [self.slot_name[s] for s, f in enumerate(first) if f > len(self.acc.rows)]
+            raise RuntimeError("Missing predictions: " + ", ".join(f"sentence {sid} in image {img}" for img, sid in lost[:20])
+                               + (" ..." if len(lost) > 20 else ""))
+        self.results = OrderedDict()
+        score = {}
+        order = [c for c in sorted(range(C), key=lambda c: self.categories[c]) if tot[c] > 0]     # "all" sorts among the types
+        for j, k in enumerate(self.topk):
+            header = "Upper_bound" if k == -1 else f"Recall@{k}"
+            self.results[k] = {self.categories[c]: pos[j * C + c] / tot[c] for c in order}
+            for c in order:
+                score[f"{header}_{self.categories[c]}"] = pos[j * C + c] / tot[c]
+        return score
+
+    @staticmethod
+    def write_results(score, path):
+        """`write_flickr_results` (engine/inference.py:368-381): bbox.csv."""
+        lines = ["metric, avg "] + [f"{name}, {value} " for name, value in score.items()]
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")

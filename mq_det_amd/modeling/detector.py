@@ -23,8 +23,8 @@ from . import pipeline
 from .device_model import DeviceModel, compute_dtype  # noqa: F401  (compute_dtype: re-exported)
 from .graph_runner import Memo
 from .params import Container, build_param_tree
-from .query_selector import (build_token_index, consume_text_dropout_draws, prepare_positive_map, text_dropout_mask,
-                             text_dropout_rate)
+from .query_selector import (build_item_token_index, build_token_index, consume_text_dropout_draws, prepare_positive_map,
+                             text_dropout_mask, text_dropout_rate)
 
 
 def expand_bbox(box_list, expand_ratio=1.5):
@@ -528,6 +528,63 @@ class GeneralizedVLRCNN_New(DeviceModel):
             result.append(bl)
         return result
 
+    # ------------------------------------------------------------------ phrase grounding: one caption and one positive map per image
+    @torch.no_grad()
+    def forward_grounding(self, images, captions, positive_maps, return_raw=False):
+        """The grounding protocol (`TEST.EVAL_TASK = "grounding"`, engine/inference.py:615-625) for a BATCH: `captions` = B different
+        strings, `positive_maps` = B dicts {label: [token positions]} of any sizes.  Item i equals `model(ImageList(images.tensors[i:i+1],
+        images.image_sizes[i:i+1]), captions=[captions[i]], positive_map=positive_maps[i])[0]` on the same padded canvas up to summation
+        order (the reference asserts one image per batch, :622), but the batch is ONE launch sequence through `_full_program` / `_run`,
+        HIP graphs as in `forward`: per-item vision queries (`query_selector.select`), per-item [MASK]ed ids (`_masked_ids`), the
+        per-item token index and label table `forward_chunks` passes to the scoring kernels.  The live text length is the longest
+        caption's.  -> list[BoxList] (with VISION_QUERY.RETURN_ATTN_GATE_VALUE: (list, gates) like `forward`), or the raw dict."""
+        if self.training:
+            raise NotImplementedError("training forward is out of scope")
+        images = to_image_list(images)
+        dev = images.tensors.device
+        P, cfg = self._ensure_plan(dev), self.cfg
+        dtype = P["backbone.body.patch_embed.proj.weight"].dtype
+        Bn = images.tensors.shape[0]
+        if len(captions) != Bn or len(positive_maps) != Bn:
+            raise ValueError(f"forward_grounding: {Bn} images, {len(captions)} captions, {len(positive_maps)} positive maps")
+        onehot = str(cfg.MODEL.DYHEAD.get("SCORE_AGG", "MEAN")).upper() == "ONEHOT"
+        ids, ams, kvs, pms, labs, smaps = [], [], [], [], [], []
+        for cap, pm in zip(captions, positive_maps):
+            i, a, kv = self.tokenize([cap], dev)
+            pm, lab, pm_key, smap, slab, kv = prepare_positive_map(pm, i.shape[1], kv, onehot)
+            i, _, _ = self._masked_ids(i, (cap,), pm_key, lab, pm, dev)
+            ids.append(i)
+            ams.append(a)
+            kvs.append(kv)
+            pms.append(pm)
+            labs.append(lab)
+            smaps.append((smap, slab))
+        T = ids[0].shape[1]
+        max_kv = max(kvs) if min(kvs) > 0 else 0
+        Tl = self._live_len(T, max_kv)                            # live-row compaction (see forward): the batch's longest caption
+        input_ids, attention_mask = torch.cat(ids)[:, :Tl].contiguous(), torch.cat(ams)[:, :Tl].contiguous()
+        vision = idx = None
+        if self._use_vq():
+            vision, idx = self.query_selector.select(labs, pms, Tl, dev, dtype)
+            if vision.shape[1] == 0:                              # no label of any caption has a vision query: text only
+                vision = idx = None
+        tok3, lab2 = build_item_token_index(smaps)
+        tail = (input_ids, attention_mask, vision, idx, tok3.to(dev), lab2.to(dev), self._im_wh(images, dev), max_kv)
+        if return_raw:
+            x = images.tensors.to(dtype).contiguous(memory_format=torch.channels_last)
+            raw = self._full_program(x, *tail, want_raw=True)
+            return self._pad_raw_text(raw, T) if Tl < T else raw
+        out = self._run("_full_program", (self._pixels(images.tensors, dtype),) + tail, self.use_hip_graph and not _ops.timing_active())
+        self.last_packed = packed = out["packed"].clone()         # (cloned: under replay `out` are the graph's static buffers)
+        gates = out["gates"]
+        if gates is not None:
+            counts = torch.cat([out["counts"].float(), gates.float()]).tolist()
+            counts, gates = [int(c) for c in counts[:Bn]], counts[Bn:]
+        else:
+            counts = out["counts"].tolist()                       # the one device->host sync of the forward
+        result = self._boxlists(packed, self._split_counts(counts), images.image_sizes)
+        return (result, gates) if cfg.VISION_QUERY.RETURN_ATTN_GATE_VALUE else result
+
     # ------------------------------------------------------------------ chunk batching (SURVEY.md 8f-1)
     def _features(self, images):
         """(feats, pooled) of an image batch through the per-image cache (Swin + FPN run once per distinct tensor)."""
@@ -618,14 +675,7 @@ class GeneralizedVLRCNN_New(DeviceModel):
                      "hidden": [rep(torch.cat([live(f["hidden"][k]) for f in fronts])) for k in range(len(fronts[0]["hidden"]))],
                      "key_bias": rep(torch.cat([live(f["key_bias"]) for f in fronts])), "kv_len": rep(torch.cat([f["kv_len"] for f in fronts])),
                      "next": fronts[0]["next"]}
-            L = max(1, max(len(l) for _, l in smaps))
-            MT = max(1, max((len(pm[k]) for pm, l in smaps for k in l), default=1))
-            tok3 = torch.full((g, L, MT), -1, dtype=torch.int32)
-            lab2 = torch.zeros(g, L, dtype=torch.int32)
-            for c, (pm, l) in enumerate(smaps):
-                for j, k in enumerate(l):
-                    tok3[c, j, :len(pm[k])] = torch.tensor(pm[k], dtype=torch.int32)
-                    lab2[c, j] = k
+            tok3, lab2 = build_item_token_index(smaps)
             tok3, lab2 = rep(tok3.to(dev)).contiguous(), rep(lab2.to(dev)).contiguous()
             tile = lambda f: f.permute(0, 2, 3, 1).repeat(g, 1, 1, 1).permute(0, 3, 1, 2)     # noqa: E731  NHWC memory kept
             inputs = ([tile(f) for f in feats], None if pooled is None else pooled.repeat(g, 1, 1), front, rep(torch.cat(ids)),

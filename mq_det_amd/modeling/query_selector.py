@@ -34,6 +34,21 @@ def build_token_index(positive_map, labels, device):
     return idx.to(device, non_blocking=True), ids.to(device, non_blocking=True)
 
 
+def build_item_token_index(score_maps):
+    """`build_token_index` for items that each score their own map (forward_chunks: one per chunk; forward_grounding: one per image):
+    score_maps = [(map, labels)] -> host tensors tok3 [items, L, MT] int32 token positions (-1 padded, also the rows of an item with fewer
+    than L labels) and lab2 [items, L] int32 label ids (0 padded), L / MT = the largest label count / token count."""
+    L = max(1, max(len(l) for _, l in score_maps))
+    MT = max(1, max((len(pm[k]) for pm, l in score_maps for k in l), default=1))
+    tok3 = torch.full((len(score_maps), L, MT), -1, dtype=torch.int32)
+    lab2 = torch.zeros(len(score_maps), L, dtype=torch.int32)
+    for c, (pm, l) in enumerate(score_maps):
+        for j, k in enumerate(l):
+            tok3[c, j, :len(pm[k])] = torch.tensor(pm[k], dtype=torch.int32)
+            lab2[c, j] = k
+    return tok3, lab2
+
+
 def prepare_positive_map(positive_map, T, max_kv=0, onehot=False):
     """What a forward needs from the caller's `{label: [token positions]}` for a caption of T positions; returns
     (positive_map, labels_in_caption, pm_key, score_map, score_labels, max_kv):

@@ -74,6 +74,8 @@ _SIGNATURES = {
     "mq_lvis_accumulate": (_i, [_vp] * 7 + [_i, _vp]),
     "mq_coco_match": (_i, [_vp] * 12 + [_i, _l, _vp]),
     "mq_coco_accumulate": (_i, [_vp] * 9 + [_i, _vp]),
+    "mq_flickr_recall": (_i, [_vp] * 7 + [_i, _i, _vp]),
+    "mq_flickr_tally": (_i, [_vp] * 5 + [_i, _i, _i, _vp]),
     "mq_bank_admit": (_i, [_vp] * 8 + [_i] * 8 + [_f, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
@@ -1659,6 +1661,44 @@ def coco_accumulate(cat_off, order, rank, dt_bits, num_gt, rec_thr):
         _chk(lib.mq_coco_accumulate(_ptr(cat_off), _ptr(order), _ptr(rank), _ptr(dt_bits), _ptr(num_gt), _ptr(max_dets), _ptr(rec_thr),
                                     _ptr(precision), _ptr(recall), K, _stream()), "mq_coco_accumulate")
     return precision, recall
+
+
+# ---- Flickr30k Entities Recall@k (csrc/flickr_eval.hip; host side: mq_det_amd/evaluation.py FlickrRecallEvaluator)
+FLICKR_MAX_K = 30
+
+
+def flickr_recall(phrase_dt, phrase_gt, dt_box, gt_box, ks, iou_thr):
+    """`box_iou(pred, gt)[:k].max() >= iou_thresh` for every phrase and every k of `ks` (iou_thr: [1] fp64 on the device) -> hits [P] int32, bit j = hit at ks[j].  Layouts:
+    include/mqdet_hip.h mq_flickr_recall."""
+    lib = load_library()
+    _need_gpu(phrase_dt, phrase_gt, dt_box, gt_box, ks, iou_thr)
+    assert phrase_dt.dtype == phrase_gt.dtype == ks.dtype == torch.int32 and dt_box.dtype == torch.float32 and gt_box.dtype == iou_thr.dtype == torch.float64
+    assert iou_thr.numel() == 1
+    for t in (phrase_dt, phrase_gt, dt_box, gt_box, ks):
+        assert t.is_contiguous()
+    P, NK = len(phrase_dt), ks.numel()
+    assert len(phrase_gt) == P and phrase_dt.shape[1:] == phrase_gt.shape[1:] == (2,) and 1 <= NK <= FLICKR_MAX_K
+    assert dt_box.shape[1:] == gt_box.shape[1:] == (4,)
+    hits = torch.zeros(P, dtype=torch.int32, device=gt_box.device)
+    with _timed("flickr_recall"):
+        _chk(lib.mq_flickr_recall(_ptr(phrase_dt), _ptr(phrase_gt), _ptr(dt_box), _ptr(gt_box), _ptr(ks), _ptr(iou_thr), _ptr(hits), P, NK, _stream()), "mq_flickr_recall")
+    return hits
+
+
+def flickr_tally(hits, cat_off, cat_idx, num_k, num_cat):
+    """RecallTracker's counts -> (positives [num_k, num_cat], totals [num_cat]) int64; column 0 is the implicit category "all".  Layouts:
+    include/mqdet_hip.h mq_flickr_tally."""
+    lib = load_library()
+    _need_gpu(hits, cat_off, cat_idx)
+    assert hits.dtype == cat_off.dtype == cat_idx.dtype == torch.int32 and hits.is_contiguous() and cat_off.is_contiguous() and cat_idx.is_contiguous()
+    P = len(hits)
+    assert len(cat_off) == P + 1 and 1 <= num_k <= FLICKR_MAX_K and num_cat >= 1
+    positives = torch.zeros(num_k, num_cat, dtype=torch.int64, device=hits.device)
+    totals = torch.zeros(num_cat, dtype=torch.int64, device=hits.device)
+    with _timed("flickr_tally"):
+        _chk(lib.mq_flickr_tally(_ptr(hits), _ptr(cat_off), _ptr(cat_idx), _ptr(positives), _ptr(totals), P, int(num_k), int(num_cat), _stream()),
+             "mq_flickr_tally")
+    return positives, totals
 
 
 # ---- vision-query bank (csrc/query_bank.hip; host side: mq_det_amd/query_bank.py QueryBank)

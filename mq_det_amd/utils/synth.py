@@ -152,3 +152,55 @@ def synthetic_coco(n_img=5000, n_cat=80, gt_per_img=7.0, det_per_img=100, seed=0
         s = slice(i * det_per_img, (i + 1) * det_per_img)
         preds.append((int(img_ids[i]), (int(pwh[i, 0]), int(pwh[i, 1])), boxes[s], scores[s], lab[s].astype(np.int64)))
     return gt, preds
+
+
+FLICKR_TYPES = ("people", "clothing", "bodyparts", "animals", "vehicles", "instruments", "scene", "other")
+
+
+def synthetic_flickr(n_img=1000, sent_per_img=5, phrases_per_sent=3.0, det_per_sent=300, seed=0, hit_frac=0.5, max_gt=3, score_levels=0,
+                     same_size=False):
+    """Seeded Flickr30k-Entities-shaped ground truth, as `FlickrRecallEvaluator` takes it, and detections as the model returns them:
+    -> (gt {image id: [sentence = list of {"phrase_id", "phrase_type"}]}, boxes {image id: {phrase id: [[x1, y1, x2, y2] ints]}},
+    preds [(image id, sentence id, (width, height) of the network input, (height, width) of the image, number of phrases, boxes xyxy float32
+    [n, 4] at the input size, scores float32 [n], phrase index int64 [n])]).  A sentence has 1 + Poisson(phrases_per_sent - 1) phrases (at most
+    10) of 1 .. max_gt boxes and one or two types, and up to `det_per_sent` detections; a `hit_frac` share of them are jittered copies of a
+    ground truth of their phrase, the rest are random.  score_levels > 0 quantises the scores so that ties occur; same_size: the network
+    input has the image's size (ratio 1)."""
+    import numpy as np
+    g = np.random.default_rng(seed)
+    gt, boxes, preds = {}, {}, []
+    for i in range(n_img):
+        img = str(100000 + 7 * i)
+        w, h = int(g.integers(320, 641)), int(g.integers(320, 641))
+        nw, nh = (w, h) if same_size else (int(g.integers(400, 1334)), int(g.integers(400, 801)))
+        gt[img], boxes[img] = [], {}
+        for s in range(sent_per_img):
+            n_ph = int(min(10, 1 + g.poisson(max(phrases_per_sent - 1, 0))))
+            sent, gts = [], []
+            for p in range(n_ph):
+                pid = str(1000 * s + p)
+                k = int(g.integers(1, max_gt + 1))
+                bw, bh = g.integers(8, w // 2, k), g.integers(8, h // 2, k)
+                x, y = (g.random(k) * (w - bw)).astype(np.int64), (g.random(k) * (h - bh)).astype(np.int64)
+                b = np.stack([x, y, x + bw, y + bh], 1)
+                boxes[img][pid] = b.tolist()
+                gts.append(b.astype(np.float64))
+                types = list(g.choice(FLICKR_TYPES, 1 + int(g.random() < 0.15), replace=False))
+                sent.append({"phrase_id": pid, "phrase_type": [str(t) for t in types]})
+            gt[img].append(sent)
+            n = int(g.integers(det_per_sent // 2, det_per_sent + 1)) if det_per_sent > 1 else det_per_sent
+            ph = g.integers(0, n_ph, n)
+            hit = g.random(n) < hit_frac
+            b = np.empty((n, 4))
+            rw, rh = g.random(n) * w * 0.5 + 2, g.random(n) * h * 0.5 + 2
+            rx, ry = g.random(n) * (w - rw), g.random(n) * (h - rh)
+            b[:] = np.stack([rx, ry, rx + rw, ry + rh], 1)
+            for d in np.nonzero(hit)[0]:
+                src = gts[ph[d]]
+                b[d] = src[int(g.integers(len(src)))] + g.normal(0, 6, 4)
+            sc = g.random(n)
+            if score_levels:
+                sc = np.floor(sc * score_levels) / score_levels
+            ratio = np.array([nw / w, nh / h, nw / w, nh / h])
+            preds.append((img, s, (nw, nh), (h, w), n_ph, (b * ratio).astype(np.float32), sc.astype(np.float32), ph.astype(np.int64)))
+    return gt, boxes, preds
