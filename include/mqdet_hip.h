@@ -469,6 +469,21 @@ int mq_tta_merge_prep(const float* packed, const int* counts, const float* tpara
 int mq_tta_merge_finalize(const float* boxes_s, const float* scores_s, const int* labels_s, const int* src_s, const unsigned char* keep,
                           const int* nvalid, float* thr, const int* cls_rank, float* boxes_o, float* scores_o, long long* labels_o, int* counts, int B, int N,
                           int top_n, void* stream);
+/* mq_tta_merge_special: TEST.SPECIAL_NMS = 'soft-nms' (mode 1, aux = sigma), 'vote' (2), 'soft-vote' (3, aux = MODEL.RETINANET.INFERENCE_TH
+ *   > 0) on the rows mq_tta_merge_prep left, one workgroup per (image, class-list position 0 .. L - 1); thresh = TEST.TH > 0.  -> per slot
+ *   of the sorted list: boxes_m [B, N, 4], scores_m [B, N] fp32, keep [B, N] uint8, seq [B, N] int32 = the row's place inside its class
+ *   (written for the first nvalid[b] slots).  A class of up to cap rows (1 .. 4096) is staged in LDS (36 bytes a row), a larger one in its
+ *   slice of ws [B, N, 9] fp32 (NULL allowed when N <= cap) and counted in nws [1] int32 (zeroed by the caller).  Equal scores: the lower
+ *   original row first.  -1: arguments out of range.
+ * mq_tta_merge_finalize_special: mq_tta_merge_finalize for those rows: the top_n cut over scores_m (which are not in list order), then
+ *   the rows ordered by (class-list position, seq).  Arguments as mq_tta_merge_finalize.
+ * Replaces box_aug.py:209-349 (boxlist_nms with 'soft-nms' / 'vote' / 'soft-vote', bbox_vote, soft_bbox_vote) and csrc/cpu/soft_nms.cpp. */
+int mq_tta_merge_special(const float* boxes_s, const float* scores_s, const int* labels_s, const int* src_s, const int* nvalid,
+                         const int* cls_rank, float* boxes_m, float* scores_m, unsigned char* keep, int* seq, float* ws, int* nws, int B,
+                         int N, int L, int mode, float thresh, float aux, int cap, void* stream);
+int mq_tta_merge_finalize_special(const float* boxes_m, const float* scores_m, const int* labels_s, const int* seq,
+                                  const unsigned char* keep, const int* nvalid, float* thr, const int* cls_rank, float* boxes_o,
+                                  float* scores_o, long long* labels_o, int* counts, int B, int N, int top_n, void* stream);
 
 /* ---- LVIS Fixed AP (csrc/lvis_eval.hip, host side mq_det_amd/evaluation.py LvisFixedAPEvaluator).  fp64 / fp32 / integer data only.
  * mq_lvis_match: LVISEval.evaluate_img for P (image, category) pairs.  pair_dt / pair_gt [P, 2] int32 = (first, count) of the pair's detections

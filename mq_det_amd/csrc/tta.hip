@@ -9,6 +9,10 @@
 // mq_tta_merge_*: box_aug.py merge_result_from_multi_scales with SPECIAL_NMS = 'none', after the per-transform un-flip / area band /
 // rescale, as four launches around mq_ml_nms (post.hip).  Every sort is a rank by counting over a total order, so the result does not
 // depend on the schedule.
+//
+// mq_tta_merge_special / mq_tta_merge_finalize_special: the same merge with SPECIAL_NMS = 'soft-nms', 'vote' or 'soft-vote': the per-class
+// step in place of mq_ml_nms, one workgroup per (image, class), and a finalize whose cut ranks the new scores (see "special merges" below;
+// ties on equal scores go to the lower original row, where the reference's order is whatever numpy's unstable argsort leaves).
 #include "common.h"
 
 MQ_NAMESPACE_BEGIN
@@ -297,6 +301,280 @@ extern "C" int mq_tta_merge_finalize(const float* boxes_s, const float* scores_s
   MQ_CHECK_LAUNCH();
   hipLaunchKernelGGL(tta_rank_final_kernel, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, boxes_s, scores_s, labels_s, src_s,
                      keep, nvalid, thr, cls_rank, boxes_o, scores_o, labels_o, counts, N);
+  MQ_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- special merges
+// TEST.SPECIAL_NMS = 'soft-nms' / 'vote' / 'soft-vote' (box_aug.py:209-349, csrc/cpu/soft_nms.cpp): the per-class step between
+// mq_tta_merge_prep and the output ranking, one workgroup per (image, class-list position).  The workgroup gathers its class's rows from the
+// image's score-sorted list in list order (position = number of earlier rows of the class: a count, not a race), stages them -- box, +1
+// area, score, list index, original row, state -- in LDS, or, when the class has more than `cap` rows, in its own slice of a global
+// workspace (slice start = rows of earlier classes, so the slices are disjoint), and runs the reference's loop on the staged rows:
+//   soft-nms   pick the live row of the highest current score; every other live row s <- float(s * exp(-ovr^2 / sigma)) with the fp32 +1
+//              IoU and the fp64 factor; s < thresh discards the row; the picks, in pick order, with their decayed scores
+//   vote       the first live row (rows are in score order) heads a cluster of every live row with IoU >= thresh; a cluster of one passes
+//              through, a larger one becomes sum(b s) / sum(s) with the head's score; clusters in cluster order
+//   soft-vote  vote, plus every non-head member with s (1 - ovr) >= aux (MODEL.RETINANET.INFERENCE_TH) as a row of its own box and that
+//              score; the class's rows re-sorted by score
+// Every output row takes the slot of one input row (a cluster its head's), so the capacity stays N.  -> per slot: box, score, keep flag and
+// seq, the row's place inside its class, which mq_tta_merge_finalize_special ranks by.
+// IoUs are the reference's fp32 operations in its order with contraction off: every >= of the voting modes is numpy's.  The voted box is
+// summed in fp64 in a fixed order (per thread by ascending row, then a fixed tree) and rounded once; the reference sums in fp32.
+// TIES: on equal scores the reference's order follows numpy's unstable argsort and soft-NMS's swap-with-last; here the LOWER ORIGINAL ROW
+// goes first (list order for the votes, the staged original row for soft-NMS's pick and soft-vote's final sort).
+#define TTA_SP_WORDS 9                                     // 4-byte words staged per row
+#define TTA_SP_MAX_CAP 4096                                // rows of the LDS path at most: 144 KB
+enum { TTA_SOFT_NMS = 1, TTA_VOTE = 2, TTA_SOFT_VOTE = 3 };
+enum { TTA_DEAD = 0, TTA_LIVE = 1, TTA_OUT = 4 };
+
+__device__ __forceinline__ float tta_iou1(float ax1, float ay1, float ax2, float ay2, float aa, float bx1, float by1, float bx2, float by2,
+                                          float ba) {
+#pragma clang fp contract(off)                           // soft_nms.cpp:77-86 / box_aug.py:252-260, one operation at a time
+  const float xx1 = ax1 < bx1 ? bx1 : ax1, yy1 = ay1 < by1 ? by1 : ay1;
+  const float xx2 = bx2 < ax2 ? bx2 : ax2, yy2 = by2 < ay2 ? by2 : ay2;
+  float w = (xx2 - xx1) + 1.f, h = (yy2 - yy1) + 1.f;
+  w = w > 0.f ? w : 0.f;
+  h = h > 0.f ? h : 0.f;
+  const float inter = w * h;
+  return inter / ((aa + ba) - inter);
+}
+
+__device__ __forceinline__ double tta_wave_sum(double v) {
+  for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
+  return v;                                                // lane 0: the wave's sum, always the same tree
+}
+
+__global__ __launch_bounds__(256) void tta_special_kernel(const float* __restrict__ boxes_s, const float* __restrict__ scores_s,
+                                                          const int* __restrict__ labels_s, const int* __restrict__ src_s,
+                                                          const int* __restrict__ nvalid, const int* __restrict__ cls_rank,
+                                                          float* __restrict__ boxes_m, float* __restrict__ scores_m,
+                                                          unsigned char* __restrict__ keep, int* __restrict__ seq, float* __restrict__ ws,
+                                                          int* __restrict__ nws, int N, int mode, float thresh, float aux, int cap) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) float sp_s[];             // [TTA_SP_WORDS][m] when the class fits
+  __shared__ int cnt_s[2], wcnt[4], red_k[4], red_r[4];
+  __shared__ float red_s[4];
+  __shared__ double red_d[5][4];
+  const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = nvalid[b];
+  const long base = (long)b * N;
+  // rows of this class (m) and of the classes before it in the list (off)
+  if (tid < 2) cnt_s[tid] = 0;
+  __syncthreads();
+  int mc = 0, oc = 0;
+  for (int j = tid; j < n; j += 256) {
+    const int p = cls_rank[labels_s[base + j]];
+    mc += p == c;
+    oc += p < c;
+  }
+  atomicAdd(&cnt_s[0], mc);
+  atomicAdd(&cnt_s[1], oc);
+  __syncthreads();
+  const int m = cnt_s[0], off = cnt_s[1];
+  if (m == 0) return;
+  const bool in_lds = m <= cap;
+  if (!in_lds && tid == 0) atomicAdd(nws, 1);
+  float* st = in_lds ? sp_s : ws + (base + off) * TTA_SP_WORDS;
+  float *X1 = st, *Y1 = st + m, *X2 = st + 2 * (long)m, *Y2 = st + 3 * (long)m, *AR = st + 4 * (long)m, *SC = st + 5 * (long)m;
+  int *IDX = (int*)(st + 6 * (long)m), *SRC = (int*)(st + 7 * (long)m), *FL = (int*)(st + 8 * (long)m);
+  // stage: row j of the list goes to slot (rows of the class before j)
+  int run = 0;
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    const int j = j0 + tid;
+    const bool mine = j < n && cls_rank[labels_s[base + j]] == c;
+    const unsigned long long bal = __ballot(mine);
+    if (lane == 0) wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    int k = run + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wv; ++w) k += wcnt[w];
+    run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    if (mine) {
+      const float x1 = boxes_s[(base + j) * 4 + 0], y1 = boxes_s[(base + j) * 4 + 1], x2 = boxes_s[(base + j) * 4 + 2],
+                  y2 = boxes_s[(base + j) * 4 + 3];
+      X1[k] = x1;
+      Y1[k] = y1;
+      X2[k] = x2;
+      Y2[k] = y2;
+      AR[k] = ((x2 - x1) + 1.f) * ((y2 - y1) + 1.f);
+      SC[k] = scores_s[base + j];
+      IDX[k] = j;
+      SRC[k] = src_s[base + j];
+      FL[k] = TTA_LIVE;
+    }
+    __syncthreads();
+  }
+
+  if (mode == TTA_SOFT_NMS) {
+    const double sigma = (double)aux;
+    for (int picks = 0;; ++picks) {
+      // the live row of the highest current score, the lower original row on a tie
+      float bs = 0.f;
+      int bk = -1, br = 0;
+      for (int k = tid; k < m; k += 256)
+        if (FL[k] == TTA_LIVE) {
+          const float s = SC[k];
+          const int r = SRC[k];
+          if (bk < 0 || s > bs || (s == bs && r < br)) bs = s, bk = k, br = r;
+        }
+      for (int d = 32; d; d >>= 1) {
+        const float os = __shfl_down(bs, d);
+        const int ok = __shfl_down(bk, d), orow = __shfl_down(br, d);
+        if (ok >= 0 && (bk < 0 || os > bs || (os == bs && orow < br))) bs = os, bk = ok, br = orow;
+      }
+      if (lane == 0) red_s[wv] = bs, red_k[wv] = bk, red_r[wv] = br;
+      __syncthreads();
+      bs = red_s[0], bk = red_k[0], br = red_r[0];
+      for (int w = 1; w < 4; ++w)
+        if (red_k[w] >= 0 && (bk < 0 || red_s[w] > bs || (red_s[w] == bs && red_r[w] < br))) bs = red_s[w], bk = red_k[w], br = red_r[w];
+      if (bk < 0) break;                                   // nothing live: done (the same answer in every thread)
+      const float hx1 = X1[bk], hy1 = Y1[bk], hx2 = X2[bk], hy2 = Y2[bk], ha = AR[bk];
+      if (tid == 0) {                                      // the pick is never checked against the threshold
+        const long o = base + IDX[bk];
+        FL[bk] = TTA_OUT;
+        boxes_m[o * 4 + 0] = hx1;
+        boxes_m[o * 4 + 1] = hy1;
+        boxes_m[o * 4 + 2] = hx2;
+        boxes_m[o * 4 + 3] = hy2;
+        scores_m[o] = bs;
+        keep[o] = 1;
+        seq[o] = picks;
+      }
+      for (int k = tid; k < m; k += 256)
+        if (k != bk && FL[k] == TTA_LIVE) {
+          const float ovr = tta_iou1(hx1, hy1, hx2, hy2, ha, X1[k], Y1[k], X2[k], Y2[k], AR[k]);
+          const float s = (float)((double)SC[k] * exp(-((double)ovr * (double)ovr) / sigma));
+          SC[k] = s;
+          if (s < thresh) {
+            FL[k] = TTA_DEAD;
+            keep[base + IDX[k]] = 0;
+          }
+        }
+      __syncthreads();
+    }
+    return;
+  }
+
+  // vote / soft-vote
+  int head = 0;
+  for (;;) {
+    while (head < m && FL[head] != TTA_LIVE) ++head;       // rows are in score order: the first live row heads the next cluster
+    if (head >= m) break;
+    const float hx1 = X1[head], hy1 = Y1[head], hx2 = X2[head], hy2 = Y2[head], ha = AR[head], hs = SC[head];
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0., as = 0.;
+    int members = 0;
+    if (tid == 0) {                                        // the head is a member of its own cluster (ovr = 1)
+      a0 = (double)hx1 * hs, a1 = (double)hy1 * hs, a2 = (double)hx2 * hs, a3 = (double)hy2 * hs, as = hs;
+      members = 1;
+    }
+    for (int k = head + 1 + tid; k < m; k += 256)
+      if (FL[k] == TTA_LIVE) {
+        const float x1 = X1[k], y1 = Y1[k], x2 = X2[k], y2 = Y2[k], s = SC[k];
+        const float ovr = tta_iou1(hx1, hy1, hx2, hy2, ha, x1, y1, x2, y2, AR[k]);
+        if (!(ovr >= thresh)) continue;
+        a0 += (double)x1 * s, a1 += (double)y1 * s, a2 += (double)x2 * s, a3 += (double)y2 * s, as += s;
+        ++members;
+        const long o = base + IDX[k];
+        const float soft = s * (1.f - ovr);
+        if (mode == TTA_SOFT_VOTE && soft >= aux) {        // the member stays as a row of its own with the softened score
+          FL[k] = TTA_OUT;
+          SC[k] = soft;
+          for (int q = 0; q < 4; ++q) boxes_m[o * 4 + q] = boxes_s[o * 4 + q];
+          scores_m[o] = soft;
+          keep[o] = 1;
+        } else {
+          FL[k] = TTA_DEAD;
+          keep[o] = 0;
+        }
+      }
+    a0 = tta_wave_sum(a0), a1 = tta_wave_sum(a1), a2 = tta_wave_sum(a2), a3 = tta_wave_sum(a3), as = tta_wave_sum(as);
+    for (int d = 32; d; d >>= 1) members += __shfl_down(members, d);
+    if (lane == 0) red_d[0][wv] = a0, red_d[1][wv] = a1, red_d[2][wv] = a2, red_d[3][wv] = a3, red_d[4][wv] = as, red_k[wv] = members;
+    __syncthreads();
+    if (tid == 0) {
+      const long o = base + IDX[head];
+      float ob[4] = {hx1, hy1, hx2, hy2};
+      if (red_k[0] + red_k[1] + red_k[2] + red_k[3] > 1) {
+        const double den = ((red_d[4][0] + red_d[4][1]) + red_d[4][2]) + red_d[4][3];
+        for (int q = 0; q < 4; ++q) ob[q] = (float)((((red_d[q][0] + red_d[q][1]) + red_d[q][2]) + red_d[q][3]) / den);
+      }
+      for (int q = 0; q < 4; ++q) boxes_m[o * 4 + q] = ob[q];
+      scores_m[o] = hs;
+      keep[o] = 1;
+      seq[o] = head;                                       // vote: cluster order
+      FL[head] = TTA_OUT;
+    }
+    __syncthreads();
+  }
+  if (mode == TTA_SOFT_VOTE)                               // the class's rows by (score descending, original row ascending)
+    for (int k = tid; k < m; k += 256)
+      if (FL[k] == TTA_OUT) {
+        const float s = SC[k];
+        const int r = SRC[k];
+        int rank = 0;
+        for (int q = 0; q < m; ++q) rank += FL[q] == TTA_OUT && (SC[q] > s || (SC[q] == s && SRC[q] < r));
+        seq[base + IDX[k]] = rank;
+      }
+}
+
+// the top-N cut when the scores are no longer in list order: the kept row with exactly top_n - 1 kept rows ahead of it in (score
+// descending, slot ascending) holds kthvalue(scores, n - top_n + 1) -> thr [B] (-inf: no cut)
+__global__ __launch_bounds__(256) void tta_cut_rank_kernel(const float* __restrict__ scores_m, const unsigned char* __restrict__ keep,
+                                                           const int* __restrict__ nvalid, float* __restrict__ thr, int N, int top_n) {
+  __shared__ float ss[256];
+  __shared__ int sf[256];
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x, n = nvalid[b];
+  const long base = (long)b * N;
+  const bool mine = i < n && keep[base + i];
+  const float si = mine ? scores_m[base + i] : 0.f;
+  int rank = 0, total = 0;
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    const int j = j0 + threadIdx.x;
+    __syncthreads();
+    const bool fj = j < n && keep[base + j];
+    sf[threadIdx.x] = fj;
+    ss[threadIdx.x] = fj ? scores_m[base + j] : 0.f;
+    __syncthreads();
+    const int m = min(256, n - j0);
+    for (int q = 0; q < m; ++q) {
+      total += sf[q];
+      rank += sf[q] && (ss[q] > si || (ss[q] == si && j0 + q < i));
+    }
+  }
+  if (!(top_n > 0 && total > top_n)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) thr[b] = -__builtin_inff();
+    return;
+  }
+  if (mine && rank == top_n - 1) thr[b] = si;
+}
+
+// The rows mq_tta_merge_prep left (boxes_s / scores_s / labels_s / src_s [B, N], nvalid [B]) -> per slot boxes_m [B, N, 4], scores_m [B, N]
+// fp32, keep [B, N] uint8, seq [B, N] int32 (written for the first nvalid[b] slots of image b).  L = length of the class list (cls_rank
+// maps a label to 0 .. L - 1); mode 1 soft-nms (aux = sigma), 2 vote, 3 soft-vote (aux = MODEL.RETINANET.INFERENCE_TH > 0); thresh > 0.
+// cap: rows of a class staged in LDS at most (1 .. 4096); a larger class works in ws [B, N, 9] fp32 (may be NULL when N <= cap) and is
+// counted in nws [1] int32 (ZEROED by the caller).  -1: arguments out of range.
+extern "C" int mq_tta_merge_special(const float* boxes_s, const float* scores_s, const int* labels_s, const int* src_s, const int* nvalid,
+                                    const int* cls_rank, float* boxes_m, float* scores_m, unsigned char* keep, int* seq, float* ws, int* nws,
+                                    int B, int N, int L, int mode, float thresh, float aux, int cap, void* stream) {
+  if (B <= 0 || N <= 0 || L <= 0) return 0;
+  if (B > 65535 || N > (1 << 24) || mode < TTA_SOFT_NMS || mode > TTA_SOFT_VOTE || !(thresh > 0.f) || cap < 1 || cap > TTA_SP_MAX_CAP) return -1;
+  if ((mode == TTA_SOFT_VOTE || mode == TTA_SOFT_NMS) && !(aux > 0.f)) return -1;
+  if (N > cap && !ws) return -1;
+  const size_t smem = (size_t)(cap < N ? cap : N) * TTA_SP_WORDS * sizeof(float);
+  return mq_launch<tta_special_kernel>(dim3(L, B), dim3(256), smem, (hipStream_t)stream, boxes_s, scores_s, labels_s, src_s, nvalid, cls_rank,
+                                       boxes_m, scores_m, keep, seq, ws, nws, N, mode, thresh, aux, cap);
+}
+
+// mq_tta_merge_finalize for the rows of mq_tta_merge_special: the cut over the new scores, then the output order (class-list position, seq).
+extern "C" int mq_tta_merge_finalize_special(const float* boxes_m, const float* scores_m, const int* labels_s, const int* seq,
+                                             const unsigned char* keep, const int* nvalid, float* thr, const int* cls_rank, float* boxes_o,
+                                             float* scores_o, long long* labels_o, int* counts, int B, int N, int top_n, void* stream) {
+  if (B <= 0 || N <= 0) return 0;
+  if (B > 65535) return -1;
+  const dim3 grid((N + 255) / 256, B);
+  hipLaunchKernelGGL(tta_cut_rank_kernel, grid, dim3(256), 0, (hipStream_t)stream, scores_m, keep, nvalid, thr, N, top_n);
+  MQ_CHECK_LAUNCH();
+  hipLaunchKernelGGL(tta_rank_final_kernel, grid, dim3(256), 0, (hipStream_t)stream, boxes_m, scores_m, labels_s, seq, keep, nvalid, thr,
+                     cls_rank, boxes_o, scores_o, labels_o, counts, N);
   MQ_CHECK_LAUNCH();
   return 0;
 }

@@ -70,6 +70,8 @@ _SIGNATURES = {
     "mq_tta_ingest_fwd": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp, _i, _i, _vp]),
     "mq_tta_merge_prep": (_i, [_vp] * 5 + [_i] + [_vp] * 10 + [_i, _i, _i, _vp]),
     "mq_tta_merge_finalize": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
+    "mq_tta_merge_special": (_i, [_vp] * 12 + [_i, _i, _i, _i, _f, _f, _i, _vp]),
+    "mq_tta_merge_finalize_special": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
     "mq_lvis_match": (_i, [_vp] * 13 + [_i, _l, _vp]),
     "mq_lvis_accumulate": (_i, [_vp] * 7 + [_i, _vp]),
     "mq_coco_match": (_i, [_vp] * 12 + [_i, _l, _vp]),
@@ -1550,11 +1552,22 @@ def tta_ingest(src, src_off, meta, bounds, coef, B, Hp, Wp, TH, R, mean, std, bg
     return out, out_f
 
 
-def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n):
+TTA_SPECIAL_MODES = {"none": 0, "soft-nms": 1, "vote": 2, "soft-vote": 3}      # TEST.SPECIAL_NMS -> mode of mq_tta_merge_special
+TTA_SOFT_NMS_SIGMA = 0.95                      # box_aug.py:228
+TTA_SPECIAL_ROW_CAP = 1024                     # rows of one class staged in LDS (36 KB); a larger class works in the global workspace
+TTA_SPECIAL_MAX_CAP = 4096
+
+
+def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n, mode="none", aux=0.0, row_cap=None, stats=None):
     """packed [T, B, K, 6] fp32, counts [T, B] int32, tparam [T, B, 4] fp32, band [T, 2] fp32 or None, cls_rank [L] int32 (-1 = dropped) ->
-    (boxes [B, N, 4], scores [B, N], labels [B, N] int64, counts [B] int32, dropped-by-class [B] int32); rows past counts[b] are junk."""
+    (boxes [B, N, 4], scores [B, N], labels [B, N] int64, counts [B] int32, dropped-by-class [B] int32); rows past counts[b] are junk.
+    mode: TEST.SPECIAL_NMS ('none' = per-class NMS; 'soft-nms', 'vote', 'soft-vote' = mq_tta_merge_special, aux = MODEL.RETINANET.INFERENCE_TH
+    for 'soft-vote').  row_cap: rows of a class the special modes stage in LDS (default TTA_SPECIAL_ROW_CAP); stats: a dict that receives
+    "workspace_classes", an int32 [1] device tensor = (image, class) segments that went through the global workspace instead."""
     lib = load_library()
     _need_gpu(packed, counts, tparam, band, cls_rank)
+    if mode not in TTA_SPECIAL_MODES:
+        raise ValueError(f"TEST.SPECIAL_NMS = {mode!r}: one of {sorted(TTA_SPECIAL_MODES)}")
     T, B, K, _ = packed.shape
     N, dev = T * K, packed.device
     assert packed.dtype == torch.float32 and packed.is_contiguous() and counts.dtype == torch.int32 and cls_rank.dtype == torch.int32
@@ -1567,16 +1580,47 @@ def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n):
     _chk(lib.mq_tta_merge_prep(_ptr(packed), _ptr(counts), _ptr(tparam), _ptr(band), _ptr(cls_rank), cls_rank.numel(), _ptr(boxes), _ptr(scores),
                                _ptr(labels), _ptr(valid), _ptr(boxes_s), _ptr(scores_s), _ptr(labels_s), _ptr(src_s), _ptr(nvalid),
                                _ptr(ndrop), T, B, K, _stream()), "mq_tta_merge_prep")
+    boxes_o, scores_o, labels_o, thr = f(B, N, 4), f(B, N), torch.empty(B, N, dtype=torch.int64, device=dev), f(B)
+    if thresh > 0 and mode != "none":
+        return _tta_merge_special(lib, boxes_s, scores_s, labels_s, src_s, nvalid, cls_rank, thr, boxes_o, scores_o, labels_o, n_out, ndrop,
+                                  float(thresh), int(top_n), mode, float(aux), row_cap, stats)
     if thresh > 0:                             # boxlist_nms: thresh <= 0 returns the rows as they are
         if N > TTA_MERGE_MAX_ROWS:
             raise ValueError(f"TTA merge: {N} rows per image (transforms x detection slots) exceed the {TTA_MERGE_MAX_ROWS} of mq_ml_nms")
         keep = ml_nms(boxes_s, labels_s, nvalid, thresh, as_bool=False)           # max_keep 0: the full sweep, never the early stop
     else:
         keep = torch.ones(B, N, dtype=torch.uint8, device=dev)
-    boxes_o, scores_o, labels_o, thr = f(B, N, 4), f(B, N), torch.empty(B, N, dtype=torch.int64, device=dev), f(B)
     _chk(lib.mq_tta_merge_finalize(_ptr(boxes_s), _ptr(scores_s), _ptr(labels_s), _ptr(src_s), _ptr(keep), _ptr(nvalid), _ptr(thr),
                                    _ptr(cls_rank), _ptr(boxes_o), _ptr(scores_o), _ptr(labels_o), _ptr(n_out), B, N, int(top_n), _stream()),
          "mq_tta_merge_finalize")
+    return boxes_o, scores_o, labels_o, n_out, ndrop
+
+
+def _tta_merge_special(lib, boxes_s, scores_s, labels_s, src_s, nvalid, cls_rank, thr, boxes_o, scores_o, labels_o, n_out, ndrop, thresh, top_n,
+                       mode, aux, row_cap, stats):
+    """The per-class step of 'soft-nms' / 'vote' / 'soft-vote' between mq_tta_merge_prep and the output ranking (csrc/tta.hip)."""
+    B, N = scores_s.shape
+    dev = scores_s.device
+    cap = TTA_SPECIAL_ROW_CAP if row_cap is None else int(row_cap)
+    if not 1 <= cap <= TTA_SPECIAL_MAX_CAP:
+        raise ValueError(f"TTA merge: row_cap {cap} outside 1 .. {TTA_SPECIAL_MAX_CAP}")
+    if mode == "soft-vote" and not aux > 0:
+        # a member with s (1 - ovr) >= a threshold <= 0 always stays: the head would too and a cluster would return more rows than it had
+        raise ValueError(f"MODEL.RETINANET.INFERENCE_TH = {aux} must be > 0 for TEST.SPECIAL_NMS = 'soft-vote' (the merge keeps its row capacity)")
+    L = cls_rank.numel()                       # >= the length of the class list (distinct labels): a position past it finds no rows
+    boxes_m, scores_m = torch.empty_like(boxes_s), torch.empty_like(scores_s)
+    keep, seq = torch.empty(B, N, dtype=torch.uint8, device=dev), torch.empty(B, N, dtype=torch.int32, device=dev)
+    ws = torch.empty(B, N, 9, dtype=torch.float32, device=dev) if N > cap else None
+    nws = torch.zeros(1, dtype=torch.int32, device=dev)
+    if L > 0:
+        _chk(lib.mq_tta_merge_special(_ptr(boxes_s), _ptr(scores_s), _ptr(labels_s), _ptr(src_s), _ptr(nvalid), _ptr(cls_rank), _ptr(boxes_m),
+                                      _ptr(scores_m), _ptr(keep), _ptr(seq), _ptr(ws), _ptr(nws), B, N, L, TTA_SPECIAL_MODES[mode], thresh,
+                                      TTA_SOFT_NMS_SIGMA if mode == "soft-nms" else aux, cap, _stream()), "mq_tta_merge_special")
+    _chk(lib.mq_tta_merge_finalize_special(_ptr(boxes_m), _ptr(scores_m), _ptr(labels_s), _ptr(seq), _ptr(keep), _ptr(nvalid), _ptr(thr),
+                                           _ptr(cls_rank), _ptr(boxes_o), _ptr(scores_o), _ptr(labels_o), _ptr(n_out), B, N, top_n, _stream()),
+         "mq_tta_merge_finalize_special")
+    if stats is not None:
+        stats["workspace_classes"] = nws
     return boxes_o, scores_o, labels_o, n_out, ndrop
 
 

@@ -7,6 +7,8 @@ maskrcnn_benchmark/data/datasets/evaluation/box_aug.py:12-63 with SPECIAL_NMS = 
   * one model(ImageList, captions, positive_map) per transform, 2 x len(TEST.SCALES) with TEST.FLIP;
   * the detections of all transforms are un-flipped, band-filtered, rescaled and merged (per-class NMS at TEST.TH, top TEST.PRE_NMS_TOP_N
     with ties) by mq_tta_merge_prep / mq_ml_nms / mq_tta_merge_finalize, straight from model.last_packed (box_aug.py:21-63, 150-238).
+`merge` / `merge_result_from_multi_scales` also take TEST.SPECIAL_NMS = 'soft-nms', 'vote' and 'soft-vote' (mq_tta_merge_special; box_aug.py:209-349);
+`im_detect_bbox_aug` itself still refuses them (check_supported).
 The forwards run eagerly: the default scales give 12 canvas shapes per batch, more than MODEL.HIP_GRAPH_CACHE keeps, so replaying graphs
 would capture one per forward (USE_HIP_GRAPH below switches them back on; tools/tta_bench.py measures both).
 """
@@ -160,9 +162,11 @@ def class_list(cfg):
     return [int(c) for c in sel] if len(sel) else list(range(1, cfg.TEST.NUM_CLASSES))
 
 
-def merge(dets, orig_wh, cfg, device):
+def merge(dets, orig_wh, cfg, device, row_cap=None, stats=None):
     """dets: per transform (packed [B, K, 6], counts [B], scaled (w, h) per image, flipped, range or None) in concatenation order ->
-    list[BoxList] of box_aug.py's merge (SPECIAL_NMS 'none')."""
+    list[BoxList] of box_aug.py's merge with TEST.SPECIAL_NMS 'none', 'soft-nms', 'vote' or 'soft-vote' (ops.tta_merge; the last three:
+    mq_tta_merge_special, csrc/tta.hip).  row_cap / stats: ops.tta_merge (the LDS row cap of the special modes, and the count of classes
+    that went through the global workspace, returned as an int in stats["workspace_classes"])."""
     global _WARNED_CLASSES
     from . import ops
     T, B = len(dets), len(orig_wh)
@@ -183,10 +187,19 @@ def merge(dets, orig_wh, cfg, device):
     for i, c in enumerate(class_list(cfg)):
         if c >= 0:
             rank[c] = i
+    mode = cfg.TEST.get("SPECIAL_NMS", "none")
+    aux = float(cfg.MODEL.get("RETINANET", {}).get("INFERENCE_TH", 0.05)) if mode == "soft-vote" else 0.0
+    if mode == "soft-vote" and cfg.TEST.TH > 0 and not aux > 0:
+        raise ValueError(f"MODEL.RETINANET.INFERENCE_TH = {aux} must be > 0 for TEST.SPECIAL_NMS = 'soft-vote': at <= 0 the reference keeps "
+                         "every member of a cluster beside the merged row, more rows than the merge has room for")
+    st = {} if stats is not None else None
     boxes, scores, labels, n_out, ndrop = ops.tta_merge(packed, counts, tparam, band, torch.from_numpy(rank).to(device), float(cfg.TEST.TH),
-                                                        int(cfg.TEST.PRE_NMS_TOP_N))
-    nd = torch.cat([n_out, ndrop]).tolist()
-    n_out, ndrop = nd[:B], nd[B:]
+                                                        int(cfg.TEST.PRE_NMS_TOP_N), mode=mode, aux=aux, row_cap=row_cap, stats=st)
+    ran = st is not None and "workspace_classes" in st          # (not with 'none', nor at TEST.TH <= 0: no per-class step ran)
+    nd = torch.cat([n_out, ndrop] + ([st["workspace_classes"]] if ran else [])).tolist()      # one read-back for all three
+    if stats is not None:
+        stats["workspace_classes"] = nd[2 * B] if ran else 0
+    n_out, ndrop = nd[:B], nd[B:2 * B]
     if sum(ndrop) and not _WARNED_CLASSES:
         _WARNED_CLASSES = True
         warnings.warn(f"TTA merge dropped {sum(ndrop)} detection(s) whose labels are outside TEST.SELECT_CLASSES / range(1, TEST.NUM_CLASSES = "
@@ -198,6 +211,27 @@ def merge(dets, orig_wh, cfg, device):
         bl.add_field("labels", labels[b, :n_out[b]])
         out.append(bl)
     return out
+
+
+def merge_result_from_multi_scales(boxlists, cfg, row_cap=None, stats=None):
+    """box_aug.py:166-206 under its own name: list[BoxList] (one per image: the detections of every transform, already concatenated in the
+    image's original frame, fields "scores" and "labels") -> list[BoxList], merged per class by TEST.SPECIAL_NMS ('none', 'soft-nms', 'vote',
+    'soft-vote') at TEST.TH and cut to TEST.PRE_NMS_TOP_N, on the device the boxes live on.  For a caller that keeps the reference's own
+    im_detect_bbox_aug loop and swaps only the merge: it is `merge` with one identity transform."""
+    if not len(boxlists):
+        return []
+    device = boxlists[0].bbox.device
+    K = max(1, max(len(bl) for bl in boxlists))
+    packed = torch.zeros(len(boxlists), K, 6, dtype=torch.float32, device=device)
+    for b, bl in enumerate(boxlists):
+        n = len(bl)
+        if n:
+            x = bl.convert("xyxy")
+            packed[b, :n, :4] = x.bbox.to(device=device, dtype=torch.float32)
+            packed[b, :n, 4] = bl.get_field("scores").to(device=device, dtype=torch.float32)
+            packed[b, :n, 5] = bl.get_field("labels").to(device=device, dtype=torch.float32)
+    wh = [tuple(bl.size) for bl in boxlists]
+    return merge([(packed, [len(bl) for bl in boxlists], wh, False, None)], wh, cfg, device, row_cap=row_cap, stats=stats)
 
 
 def check_supported(model):
