@@ -484,6 +484,17 @@ int mq_tta_merge_special(const float* boxes_s, const float* scores_s, const int*
 int mq_tta_merge_finalize_special(const float* boxes_m, const float* scores_m, const int* labels_s, const int* seq,
                                   const unsigned char* keep, const int* nvalid, float* thr, const int* cls_rank, float* boxes_o,
                                   float* scores_o, long long* labels_o, int* counts, int B, int N, int top_n, void* stream);
+/* mq_tta_merge_nms: the per-class NMS of the 'none' merge at any row count, between mq_tta_merge_prep and mq_tta_merge_finalize: greedy
+ *   suppression in list order between rows of equal label at iou > thresh (the +1 IoU of mq_ml_nms, operation for operation, uncontracted)
+ *   -> keep [B, N] uint8, all of it written, byte for byte what mq_ml_nms answers for the same lists -- without its B N^2 / 8 bytes of
+ *   mask, which stop mq_ml_nms at 16 384 rows.  One workgroup per (image, class-list position 0 .. L - 1; L = length of cls_rank); the
+ *   live rows' labels are inside the class list, as mq_tta_merge_prep leaves them.  A class of up to cap rows (1 .. 4096) is staged in
+ *   LDS (24 bytes a row), a larger one in its slice of ws [B, N, 6] fp32 (NULL allowed when N <= cap) and counted in nws [1] int32
+ *   (zeroed by the caller).  N <= 2^24, B <= 65535, thresh > 0.  -1: arguments out of range.
+ * Serves TEST.USE_MULTISCALE with the reference's un-suppressed candidates (rpn/inference.py:737-742: up to 5 x PRE_NMS_TOP_N rows per
+ *   transform and image reach box_aug.py's merge). */
+int mq_tta_merge_nms(const float* boxes_s, const int* labels_s, const int* nvalid, const int* cls_rank, unsigned char* keep, float* ws,
+                     int* nws, int B, int N, int L, float thresh, int cap, void* stream);
 
 /* ---- LVIS Fixed AP (csrc/lvis_eval.hip, host side mq_det_amd/evaluation.py LvisFixedAPEvaluator).  fp64 / fp32 / integer data only.
  * mq_lvis_match: LVISEval.evaluate_img for P (image, category) pairs.  pair_dt / pair_gt [P, 2] int32 = (first, count) of the pair's detections

@@ -13,6 +13,10 @@
 // mq_tta_merge_special / mq_tta_merge_finalize_special: the same merge with SPECIAL_NMS = 'soft-nms', 'vote' or 'soft-vote': the per-class
 // step in place of mq_ml_nms, one workgroup per (image, class), and a finalize whose cut ranks the new scores (see "special merges" below;
 // ties on equal scores go to the lower original row, where the reference's order is whatever numpy's unstable argsort leaves).
+//
+// mq_tta_merge_nms: the per-class NMS of the 'none' merge for lists mq_ml_nms's N^2 bit mask cannot take (the un-suppressed candidates of
+// TEST.USE_MULTISCALE: transforms x 5 x PRE_NMS_TOP_N rows per image), one workgroup per (image, class), the same keep flags byte for
+// byte (see "per-class NMS, any N" below).
 #include "common.h"
 
 MQ_NAMESPACE_BEGIN
@@ -577,6 +581,148 @@ extern "C" int mq_tta_merge_finalize_special(const float* boxes_m, const float* 
                      cls_rank, boxes_o, scores_o, labels_o, counts, N);
   MQ_CHECK_LAUNCH();
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- per-class NMS, any N
+// mq_tta_merge_nms: what mq_ml_nms (post.hip) answers -- greedy suppression in list order between rows of equal label at iou > thresh --
+// without its [N, N / 64] bit mask, for the candidate lists of TEST.USE_MULTISCALE (transforms x 5 x PRE_NMS_TOP_N rows per image).  Built
+// like tta_special_kernel: one workgroup per (image, class-list position), the class's rows gathered in list order and staged -- box,
+// +1 area, list index -- in LDS, or in the class's own slice of a global workspace when it has more than `cap` rows.
+// The sweep takes 256 rows at a time, one per thread:
+//   a. every row is tested against the heads kept so far (a compact list, read at the same address by every lane; no barrier per head),
+//   b. the four waves resolve their 64 rows one after the other: row j of the wave is final once rows 0 .. j - 1 are, and a kept j
+//      suppresses the later lanes; the survivors are appended to the kept list in lane order (ballot prefix), then the later waves of
+//      the chunk catch up on the appended heads.
+// The kept list is compacted IN PLACE over the staged rows (kept head k <= its own row's slot, and every thread holds its row in
+// registers from the top of the chunk); in the workspace path the first 6 * cap / 5 heads live in the idle LDS instead.
+// Every decision is taken on final flags behind a barrier or inside one wave in lane order: no race decides an order.  The IoU is
+// ml_iou2 (nms2.hip) operation for operation with contraction off (post.hip's compile does not contract it either).
+#define TTA_NMS_WORDS 6                                    // 4-byte words staged per row: x1 y1 x2 y2 area index
+
+__device__ __forceinline__ float tta_iou2(float ax1, float ay1, float ax2, float ay2, float sa, float bx1, float by1, float bx2, float by2,
+                                          float sb) {
+#pragma clang fp contract(off)
+  const float left = fmaxf(ax1, bx1), right = fminf(ax2, bx2);
+  const float top = fmaxf(ay1, by1), bottom = fminf(ay2, by2);
+  const float w = fmaxf(right - left + 1.f, 0.f), h = fmaxf(bottom - top + 1.f, 0.f);
+  const float inter = w * h;
+  return inter / (sa + sb - inter);
+}
+
+__global__ __launch_bounds__(256) void tta_nms_kernel(const float* __restrict__ boxes_s, const int* __restrict__ labels_s,
+                                                      const int* __restrict__ nvalid, const int* __restrict__ cls_rank,
+                                                      unsigned char* __restrict__ keep, float* __restrict__ ws, int* __restrict__ nws, int N,
+                                                      int L, float thresh, int cap) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) float sp_s[];             // [TTA_NMS_WORDS][m] when the class fits, else kept heads [5][kc]
+  __shared__ int cnt_s[2], wcnt[4], nk_s;
+  const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = min(max(nvalid[b], 0), N);
+  const long base = (long)b * N;
+  for (long j = (long)n + c * 256 + tid; j < N; j += (long)L * 256) keep[base + j] = 0;   // rows past the list: not kept (the blocks of an image share them out)
+  if (tid < 2) cnt_s[tid] = 0;
+  if (tid == 0) nk_s = 0;
+  __syncthreads();
+  int mc = 0, oc = 0;
+  for (int j = tid; j < n; j += 256) {
+    const int l = labels_s[base + j], p = (l >= 0 && l < L) ? cls_rank[l] : -1;
+    mc += p == c;
+    oc += p >= 0 && p < c;
+    if (c == 0 && p < 0) keep[base + j] = 0;               // a label outside the class list (mq_tta_merge_prep leaves none): not kept
+  }
+  atomicAdd(&cnt_s[0], mc);
+  atomicAdd(&cnt_s[1], oc);
+  __syncthreads();
+  const int m = cnt_s[0], off = cnt_s[1];
+  if (m == 0) return;
+  const bool in_lds = m <= cap;
+  if (!in_lds && tid == 0) atomicAdd(nws, 1);
+  float* st = in_lds ? sp_s : ws + (base + off) * TTA_NMS_WORDS;
+  float *X1 = st, *Y1 = st + m, *X2 = st + 2 * (long)m, *Y2 = st + 3 * (long)m, *AR = st + 4 * (long)m;
+  int* IDX = (int*)(st + 5 * (long)m);
+  // kept heads: slot k < kc in K*, the rest in place in the staged arrays (the LDS path: all of them, K* == the staged arrays)
+  const int kc = in_lds ? m : (cap * TTA_NMS_WORDS) / 5;
+  float *K1 = in_lds ? X1 : sp_s, *K2 = in_lds ? Y1 : sp_s + kc, *K3 = in_lds ? X2 : sp_s + 2 * kc, *K4 = in_lds ? Y2 : sp_s + 3 * kc,
+        *KA = in_lds ? AR : sp_s + 4 * kc;
+  // stage: row j of the list goes to slot (rows of the class before j)
+  int run = 0;
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    const int j = j0 + tid;
+    bool mine = false;
+    if (j < n) {
+      const int l = labels_s[base + j];
+      mine = l >= 0 && l < L && cls_rank[l] == c;
+    }
+    const unsigned long long bal = __ballot(mine);
+    if (lane == 0) wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    int k = run + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wv; ++w) k += wcnt[w];
+    run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    if (mine) {
+      const float x1 = boxes_s[(base + j) * 4 + 0], y1 = boxes_s[(base + j) * 4 + 1], x2 = boxes_s[(base + j) * 4 + 2],
+                  y2 = boxes_s[(base + j) * 4 + 3];
+      X1[k] = x1;
+      Y1[k] = y1;
+      X2[k] = x2;
+      Y2[k] = y2;
+      AR[k] = (x2 - x1 + 1.f) * (y2 - y1 + 1.f);
+      IDX[k] = j;
+    }
+    __syncthreads();
+  }
+
+  int nk = 0;                                              // kept heads so far (the same in every thread)
+  for (int r0 = 0; r0 < m; r0 += 256) {
+    const int r = r0 + tid;
+    const bool have = r < m;
+    float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, ar = 0.f;
+    int idx = 0;
+    if (have) x1 = X1[r], y1 = Y1[r], x2 = X2[r], y2 = Y2[r], ar = AR[r], idx = IDX[r];
+    int alive = have, done = 0;                            // done: kept heads this row has been tested against
+    for (int s = 0; s < 4; ++s) {
+      if (wv >= s) {
+        int k = done;
+        const int k_lds = min(nk, kc);
+        for (; alive && k < k_lds; ++k)
+          if (tta_iou2(K1[k], K2[k], K3[k], K4[k], KA[k], x1, y1, x2, y2, ar) > thresh) alive = 0;
+        for (k = max(k, kc); alive && k < nk; ++k)
+          if (tta_iou2(X1[k], Y1[k], X2[k], Y2[k], AR[k], x1, y1, x2, y2, ar) > thresh) alive = 0;
+        done = nk;
+      }
+      if (wv == s) {
+        for (int j = 0; j < 64; ++j) {                     // row j of the wave is final here: rows 0 .. j - 1 have had their say
+          const int aj = __shfl(alive, j);
+          const float jx1 = __shfl(x1, j), jy1 = __shfl(y1, j), jx2 = __shfl(x2, j), jy2 = __shfl(y2, j), ja = __shfl(ar, j);
+          if (aj && alive && lane > j && tta_iou2(jx1, jy1, jx2, jy2, ja, x1, y1, x2, y2, ar) > thresh) alive = 0;
+        }
+        const unsigned long long bal = __ballot(alive);
+        if (have) keep[base + idx] = (unsigned char)alive;
+        if (alive) {
+          const int k = nk + __popcll(bal & ((1ull << lane) - 1ull));      // <= r: the slot of a row that is already in registers
+          if (k < kc) K1[k] = x1, K2[k] = y1, K3[k] = x2, K4[k] = y2, KA[k] = ar;
+          else X1[k] = x1, Y1[k] = y1, X2[k] = x2, Y2[k] = y2, AR[k] = ar;
+        }
+        if (lane == 0) nk_s = nk + __popcll(bal);
+      }
+      __syncthreads();
+      nk = nk_s;
+    }
+  }
+}
+
+// The per-class NMS of the merge at any row count: boxes_s [B, N, 4] fp32 / labels_s [B, N] int32 / nvalid [B] int32 as mq_tta_merge_prep
+// leaves them (score-sorted, every label l of a live row with 0 <= l < L and cls_rank[l] >= 0) -> keep [B, N] uint8, all of it written,
+// byte for byte mq_ml_nms(boxes_s, labels_s, nvalid, thresh).  L = length of cls_rank; cap: rows of a class staged in LDS at most
+// (1 .. 4096); a larger class works in ws [B, N, 6] fp32 (may be NULL when N <= cap) and is counted in nws [1] int32 (ZEROED by the
+// caller).  N <= 2^24, B <= 65535.  -1: arguments out of range.
+extern "C" int mq_tta_merge_nms(const float* boxes_s, const int* labels_s, const int* nvalid, const int* cls_rank, unsigned char* keep,
+                                float* ws, int* nws, int B, int N, int L, float thresh, int cap, void* stream) {
+  if (B <= 0 || N <= 0) return 0;
+  if (B > 65535 || N > (1 << 24) || L <= 0 || L > (1 << 24) || !(thresh > 0.f) || cap < 1 || cap > TTA_SP_MAX_CAP) return -1;
+  if (N > cap && !ws) return -1;
+  const size_t smem = (size_t)(cap < N ? cap : N) * TTA_NMS_WORDS * sizeof(float);
+  return mq_launch<tta_nms_kernel>(dim3(L, B), dim3(256), smem, (hipStream_t)stream, boxes_s, labels_s, nvalid, cls_rank, keep, ws, nws, N, L,
+                                   thresh, cap);
 }
 #endif
 

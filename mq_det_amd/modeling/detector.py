@@ -312,8 +312,15 @@ class GeneralizedVLRCNN_New(DeviceModel):
             return src
         return src.to(dtype).contiguous(memory_format=torch.channels_last)
 
+    def _mode_key(self):
+        return (pipeline.candidate_mode(self.cfg),)
+
     def _split_counts(self, counts):
-        """Packed per-image counts -> live slots; remembers (and warns about) images whose ties with the K-th score did not fit."""
+        """Packed per-image counts -> live slots; remembers (and warns about) images whose ties with the K-th score did not fit.
+        Candidate mode (TEST.USE_MULTISCALE, pipeline.postprocess): the counts are the plain numbers of candidates, no tie bit."""
+        if pipeline.candidate_mode(self.cfg):
+            self.last_tie_overflow = [False] * len(counts)
+            return [int(c) for c in counts]
         self.last_tie_overflow = [bool(c >> 16) for c in counts]
         if any(self.last_tie_overflow):
             import warnings
@@ -430,7 +437,10 @@ class GeneralizedVLRCNN_New(DeviceModel):
         MODEL.BACKBONE_CACHE; False = this call recomputes Swin / FPN whatever the cache holds.  The cache (f1) recognises the
         previous call's pixels by OBJECT IDENTITY + torch's version counter of `images.tensors`: a producer that refills the same
         tensor WITHOUT bumping the counter (numpy / DLPack views of its memory, `.data` writes, IPC or custom-kernel writers) must
-        pass reuse_backbone=False (or call `clear_caches()` / set MODEL.BACKBONE_CACHE False) -- nothing else can see such a write."""
+        pass reuse_backbone=False (or call `clear_caches()` / set MODEL.BACKBONE_CACHE False) -- nothing else can see such a write.
+        With cfg.TEST.USE_MULTISCALE true (read at every call; also `forward_chunks` and `forward_grounding`) the result is every image's
+        UN-SUPPRESSED candidates, as the reference's post-processor returns them under that switch (pipeline.postprocess, candidate mode:
+        no NMS, no DETECTIONS_PER_IMG cut, rows in score-descending order; `last_packed` [B, sum_l min(PRE_NMS_TOP_N, HW_l L), 6])."""
         if self.training:
             raise NotImplementedError("training forward is out of scope")
         images = to_image_list(images)

@@ -116,12 +116,18 @@ class GraphRunner:
             return tuple(self._shape_key(v) for v in obj)
         return obj
 
+    def _mode_key(self):
+        """Configuration read at every forward that changes the launches of a program (none here): part of the graph key, so a flip
+        between two calls never replays the other mode's graph."""
+        return ()
+
     def _run(self, program, inputs, use_graph):
         """Run `program(*inputs)`, as a HIP-graph replay when its static-shape key is warm.
 
         Key = the program and the SHAPES of its tensor inputs (+ the caption length in 16-token blocks, `inputs[-1]`: it selects the
         compile-time variant of the VLFuse image-side kernel, which only visits that many key blocks);
-        image sizes are a tensor input (`im_wh`) and therefore not part of the key.  A key runs eagerly for its first
+        image sizes are a tensor input (`im_wh`) and therefore not part of the key; `_mode_key()` adds what a detector reads from its
+        configuration at every forward (MQ-GLIP: the candidate mode of TEST.USE_MULTISCALE).  A key runs eagerly for its first
         `HIP_GRAPH_WARM_CALLS` calls (library autotuning, caches; cold keys never pay a capture), is captured on the next
         one and replayed afterwards.  At most `HIP_GRAPH_CACHE` graphs are kept (LRU): evicting one releases the graph,
         its static input / output buffers and its private activation pool.  The eager forward issues ~1500 launches
@@ -130,7 +136,7 @@ class GraphRunner:
         if not use_graph:
             self.cache_stats["eager"] += 1
             return fn(*inputs)
-        key = (program, self._shape_key(inputs[:-1]), -(-int(inputs[-1]) // 16))
+        key = (program, self._shape_key(inputs[:-1]), -(-int(inputs[-1]) // 16)) + tuple(self._mode_key())
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._graphs[key] = {"stage": 0, "calls": 0}

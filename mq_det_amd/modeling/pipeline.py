@@ -977,12 +977,34 @@ TIE_SLOTS = 16      # output slots behind DETECTIONS_PER_IMG for detections tied
                     # More ties than slots are cut AND flagged: `tie_overflow` [B] in the result (bit 16 of the packed counts the detector reads)
 
 
+def candidate_mode(cfg):
+    """TEST.USE_MULTISCALE: the post-processor returns its un-suppressed candidates (see postprocess)."""
+    return bool(cfg.get("TEST", {}).get("USE_MULTISCALE", False))
+
+
+def _candidate_result(boxes, scores, labels, nvalid):
+    """The result of postprocess in candidate mode from the score-sorted rows [B, tot] and their live counts."""
+    packed = torch.cat([boxes, scores[..., None], labels.float()[..., None]], -1)
+    return {"boxes": boxes, "scores": scores, "labels": labels.to(torch.int64), "counts": nvalid,
+            "tie_overflow": torch.zeros(nvalid.shape[0], dtype=torch.bool, device=nvalid.device), "packed": packed, "counts_packed": nvalid,
+            "pre_nms": {"boxes": boxes, "scores": scores, "labels": labels, "nvalid": nvalid}}
+
+
 def postprocess(cfg, head, anchors, im_wh, tokidx, label_ids, want_cls=False, level_streams=None):
     """ATSSPostProcessor.forward (rpn/inference.py:620-769) without per-image Python loops or host syncs:
     fixed-shape top-k per level, one sort, device-side NMS, fixed-shape top-(`DETECTIONS_PER_IMG` + TIE_SLOTS).
     Returns boxes [B,K2,4], scores [B,K2] (<= 0 => empty slot), labels [B,K2], counts [B] -- all on device; live slots are contiguous
-    from slot 0 (scores sorted descending, ties behind slot K - 1 directly follow it)."""
+    from slot 0 (scores sorted descending, ties behind slot K - 1 directly follow it).
+
+    CANDIDATE MODE (cfg.TEST.USE_MULTISCALE, read at every call): the reference builds this post-processor with bbox_aug_enabled =
+    TEST.USE_MULTISCALE and then skips select_over_all_levels (rpn/inference.py:737-742, 846): no per-class NMS and no DETECTIONS_PER_IMG
+    cut, every level's top PRE_NMS_TOP_N scores above INFERENCE_TH go to box_aug.py's merge.  Here: no ml_nms / post_finalize launch; the
+    result's boxes / scores / labels / "packed" are the score-sorted candidates [B, sum_l min(PRE_NMS_TOP_N, HW_l L), ...], "counts" (and
+    "counts_packed", no tie bit) their number nvalid, "tie_overflow" all False, and "pre_nms" has no "keep".  ORDER: the reference
+    concatenates the levels, each in topk(sorted=False) order, which is arbitrary; these rows are in score-descending order, ties as
+    post_sort (or the stable argsort of the torch chain) leaves them.  Only the SET of rows is comparable."""
     A = cfg.MODEL.ATSS
+    candidates = candidate_mode(cfg)
     dev = head["tbias"].device
     Bn = head["tbias"].shape[0]
     L = tokidx.shape[-2]
@@ -1030,6 +1052,11 @@ def postprocess(cfg, head, anchors, im_wh, tokidx, label_ids, want_cls=False, le
         wh32 = im_wh if (im_wh.dtype == torch.float32 and im_wh.is_contiguous()) else im_wh.float().contiguous()
         ub, us, ul, uid = ops.post_select(ranked_l, reg_l, [a.contiguous() for a in anchors], ks, lab32.contiguous(), wh32)
         boxes, scores, labels, nvalid = ops.post_sort(ub, us, ul, ks)
+        if candidates:
+            out = _candidate_result(boxes, scores, labels, nvalid)
+            if want_cls:
+                out["cls"] = cls_all
+            return out
         keep8 = ops.ml_nms(boxes, labels, nvalid, A.NMS_TH, max_keep=K2 if Kd > 0 else 0, as_bool=False)
         packed, cnt = ops.post_finalize(boxes, scores, labels, keep8, K, K2)
         out = {"boxes": packed[..., :4], "scores": packed[..., 4], "labels": packed[..., 5].to(torch.int64), "counts": cnt & 0xFFFF,
@@ -1084,6 +1111,11 @@ def postprocess(cfg, head, anchors, im_wh, tokidx, label_ids, want_cls=False, le
     labels = torch.gather(labels, 1, order.to(torch.int64)).contiguous()
     boxes = torch.gather(boxes, 1, order[:, :, None].expand(-1, -1, 4)).contiguous()
     nvalid = (scores > 0).sum(1).to(torch.int32)
+    if candidates:
+        out = _candidate_result(boxes, scores, labels, nvalid)
+        if want_cls:
+            out["cls"] = cls_all
+        return out
     # Final selection, rpn/inference.py:757-766: with more than DETECTIONS_PER_IMG survivors the reference keeps every detection whose
     # score is >= the K-th best one (torch.kthvalue + `>=`) -- detections TIED with the K-th are all kept, so an image can return more
     # than K.  Fixed shapes here: K + TIE_SLOTS output slots; the slots behind K are live only for scores equal to the K-th.

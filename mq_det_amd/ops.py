@@ -72,6 +72,7 @@ _SIGNATURES = {
     "mq_tta_merge_finalize": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
     "mq_tta_merge_special": (_i, [_vp] * 12 + [_i, _i, _i, _i, _f, _f, _i, _vp]),
     "mq_tta_merge_finalize_special": (_i, [_vp] * 12 + [_i, _i, _i, _vp]),
+    "mq_tta_merge_nms": (_i, [_vp] * 7 + [_i, _i, _i, _f, _i, _vp]),
     "mq_lvis_match": (_i, [_vp] * 13 + [_i, _l, _vp]),
     "mq_lvis_accumulate": (_i, [_vp] * 7 + [_i, _vp]),
     "mq_coco_match": (_i, [_vp] * 12 + [_i, _l, _vp]),
@@ -1556,18 +1557,26 @@ TTA_SPECIAL_MODES = {"none": 0, "soft-nms": 1, "vote": 2, "soft-vote": 3}      #
 TTA_SOFT_NMS_SIGMA = 0.95                      # box_aug.py:228
 TTA_SPECIAL_ROW_CAP = 1024                     # rows of one class staged in LDS (36 KB); a larger class works in the global workspace
 TTA_SPECIAL_MAX_CAP = 4096
+TTA_NMS_ROW_CAP = 4096                         # rows of one class mq_tta_merge_nms stages in LDS (96 KB)
+TTA_MERGE_MAX_ROWS_ANY = 1 << 24               # rows per image of every per-class merge (mq_tta_merge_nms, mq_tta_merge_special)
+TTA_NMS_PATHS = ("auto", "segmented")
 
 
-def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n, mode="none", aux=0.0, row_cap=None, stats=None):
+def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n, mode="none", aux=0.0, row_cap=None, stats=None, nms_path="auto"):
     """packed [T, B, K, 6] fp32, counts [T, B] int32, tparam [T, B, 4] fp32, band [T, 2] fp32 or None, cls_rank [L] int32 (-1 = dropped) ->
     (boxes [B, N, 4], scores [B, N], labels [B, N] int64, counts [B] int32, dropped-by-class [B] int32); rows past counts[b] are junk.
     mode: TEST.SPECIAL_NMS ('none' = per-class NMS; 'soft-nms', 'vote', 'soft-vote' = mq_tta_merge_special, aux = MODEL.RETINANET.INFERENCE_TH
     for 'soft-vote').  row_cap: rows of a class the special modes stage in LDS (default TTA_SPECIAL_ROW_CAP); stats: a dict that receives
-    "workspace_classes", an int32 [1] device tensor = (image, class) segments that went through the global workspace instead."""
+    "workspace_classes", an int32 [1] device tensor = (image, class) segments that went through the global workspace instead.
+    nms_path (mode 'none'): "auto" = mq_ml_nms up to TTA_MERGE_MAX_ROWS rows per image and mq_tta_merge_nms (one workgroup per image and
+    class, no N^2 mask; row_cap defaults to TTA_NMS_ROW_CAP, stats as above) beyond; "segmented" = mq_tta_merge_nms at any N.  Both keep
+    the same rows."""
     lib = load_library()
     _need_gpu(packed, counts, tparam, band, cls_rank)
     if mode not in TTA_SPECIAL_MODES:
         raise ValueError(f"TEST.SPECIAL_NMS = {mode!r}: one of {sorted(TTA_SPECIAL_MODES)}")
+    if nms_path not in TTA_NMS_PATHS:
+        raise ValueError(f"nms_path = {nms_path!r}: one of {TTA_NMS_PATHS}")
     T, B, K, _ = packed.shape
     N, dev = T * K, packed.device
     assert packed.dtype == torch.float32 and packed.is_contiguous() and counts.dtype == torch.int32 and cls_rank.dtype == torch.int32
@@ -1585,15 +1594,48 @@ def tta_merge(packed, counts, tparam, band, cls_rank, thresh, top_n, mode="none"
         return _tta_merge_special(lib, boxes_s, scores_s, labels_s, src_s, nvalid, cls_rank, thr, boxes_o, scores_o, labels_o, n_out, ndrop,
                                   float(thresh), int(top_n), mode, float(aux), row_cap, stats)
     if thresh > 0:                             # boxlist_nms: thresh <= 0 returns the rows as they are
-        if N > TTA_MERGE_MAX_ROWS:
-            raise ValueError(f"TTA merge: {N} rows per image (transforms x detection slots) exceed the {TTA_MERGE_MAX_ROWS} of mq_ml_nms")
-        keep = ml_nms(boxes_s, labels_s, nvalid, thresh, as_bool=False)           # max_keep 0: the full sweep, never the early stop
+        if N > TTA_MERGE_MAX_ROWS or nms_path == "segmented":
+            keep = tta_merge_nms(boxes_s, labels_s, nvalid, cls_rank, thresh, row_cap=row_cap, stats=stats)
+        else:
+            keep = ml_nms(boxes_s, labels_s, nvalid, thresh, as_bool=False)       # max_keep 0: the full sweep, never the early stop
     else:
         keep = torch.ones(B, N, dtype=torch.uint8, device=dev)
     _chk(lib.mq_tta_merge_finalize(_ptr(boxes_s), _ptr(scores_s), _ptr(labels_s), _ptr(src_s), _ptr(keep), _ptr(nvalid), _ptr(thr),
                                    _ptr(cls_rank), _ptr(boxes_o), _ptr(scores_o), _ptr(labels_o), _ptr(n_out), B, N, int(top_n), _stream()),
          "mq_tta_merge_finalize")
     return boxes_o, scores_o, labels_o, n_out, ndrop
+
+
+def tta_merge_nms(boxes_s, labels_s, nvalid, cls_rank, thresh, row_cap=None, stats=None):
+    """boxes_s [B, N, 4] fp32 sorted by score, labels_s [B, N] int32 (live rows: inside the class list cls_rank [L] int32 maps), nvalid [B]
+    int32 -> keep [B, N] uint8, what ml_nms(boxes_s, labels_s, nvalid, thresh, as_bool=False) answers, at any N <= 2^24 (mq_tta_merge_nms,
+    csrc/tta.hip).  row_cap: rows of a class staged in LDS (default TTA_NMS_ROW_CAP); stats["workspace_classes"]: int32 [1] device tensor."""
+    lib = load_library()
+    _need_gpu(boxes_s, labels_s, nvalid, cls_rank)
+    B, N, _ = boxes_s.shape
+    dev = boxes_s.device
+    assert boxes_s.is_contiguous() and labels_s.is_contiguous() and boxes_s.dtype == torch.float32 and labels_s.shape == (B, N)
+    assert labels_s.dtype == torch.int32 and nvalid.dtype == torch.int32 and cls_rank.dtype == torch.int32 and cls_rank.is_contiguous()
+    cap = TTA_NMS_ROW_CAP if row_cap is None else int(row_cap)
+    if not 1 <= cap <= TTA_SPECIAL_MAX_CAP:
+        raise ValueError(f"TTA merge: row_cap {cap} outside 1 .. {TTA_SPECIAL_MAX_CAP}")
+    if N > TTA_MERGE_MAX_ROWS_ANY:
+        raise ValueError(f"TTA merge: {N} rows per image exceed the {TTA_MERGE_MAX_ROWS_ANY} of mq_tta_merge_nms")
+    if not thresh > 0:
+        raise ValueError("mq_tta_merge_nms: thresh must be > 0 (boxlist_nms returns the rows as they are otherwise)")
+    keep = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    ws = torch.empty(B, N, 6, dtype=torch.float32, device=dev) if N > cap else None
+    nws = torch.zeros(1, dtype=torch.int32, device=dev)
+    L = cls_rank.numel()
+    if L > 0 and B > 0 and N > 0:
+        with _timed("tta_merge_nms"):
+            _chk(lib.mq_tta_merge_nms(_ptr(boxes_s), _ptr(labels_s), _ptr(nvalid), _ptr(cls_rank), _ptr(keep), _ptr(ws), _ptr(nws), B, N, L,
+                                      float(thresh), cap, _stream()), "mq_tta_merge_nms")
+    else:
+        keep.zero_()
+    if stats is not None:
+        stats["workspace_classes"] = nws
+    return keep
 
 
 def _tta_merge_special(lib, boxes_s, scores_s, labels_s, src_s, nvalid, cls_rank, thr, boxes_o, scores_o, labels_o, n_out, ndrop, thresh, top_n,

@@ -7,8 +7,16 @@ maskrcnn_benchmark/data/datasets/evaluation/box_aug.py:12-63 with SPECIAL_NMS = 
   * one model(ImageList, captions, positive_map) per transform, 2 x len(TEST.SCALES) with TEST.FLIP;
   * the detections of all transforms are un-flipped, band-filtered, rescaled and merged (per-class NMS at TEST.TH, top TEST.PRE_NMS_TOP_N
     with ties) by mq_tta_merge_prep / mq_ml_nms / mq_tta_merge_finalize, straight from model.last_packed (box_aug.py:21-63, 150-238).
-`merge` / `merge_result_from_multi_scales` also take TEST.SPECIAL_NMS = 'soft-nms', 'vote' and 'soft-vote' (mq_tta_merge_special; box_aug.py:209-349);
-`im_detect_bbox_aug` itself still refuses them (check_supported).
+`merge` / `merge_result_from_multi_scales` also take TEST.SPECIAL_NMS = 'soft-nms', 'vote' and 'soft-vote' (mq_tta_merge_special; box_aug.py:209-349).
+
+THE REFERENCE'S PROTOCOL is selected by model.cfg.TEST.USE_MULTISCALE = True, the switch its engine sets whenever it calls this function: the
+ATSS post-processor is then built with bbox_aug_enabled and skips select_over_all_levels (rpn/inference.py:737-742, 846), so every transform
+hands the merge ALL its candidates -- per level the top PRE_NMS_TOP_N scores above INFERENCE_TH, no per-class NMS, no DETECTIONS_PER_IMG cut --
+and the merge is the only suppression step.  With the switch on the detector returns those candidates (pipeline.postprocess, candidate mode),
+`im_detect_bbox_aug` merges up to transforms x 5 x PRE_NMS_TOP_N rows per image (mq_tta_merge_nms beyond the 16 384 rows of mq_ml_nms) and takes
+all four TEST.SPECIAL_NMS modes.  With the switch off (the configuration default) every transform contributes its NMS'ed top
+(DETECTIONS_PER_IMG + TIE_SLOTS) rows instead -- cheaper, and NOT the reference's result: NMS-then-merge-NMS drops candidates the merge alone
+would have kept -- and `im_detect_bbox_aug` refuses the special modes (check_supported).
 The forwards run eagerly: the default scales give 12 canvas shapes per batch, more than MODEL.HIP_GRAPH_CACHE keeps, so replaying graphs
 would capture one per forward (USE_HIP_GRAPH below switches them back on; tools/tta_bench.py measures both).
 """
@@ -24,6 +32,7 @@ from .structures import BoxList, ImageList
 USE_HIP_GRAPH = False          # graphs for the TTA forwards (the model's MODEL.USE_HIP_GRAPH still has to allow them)
 TIMING = None                  # a dict: filled with device-event milliseconds {"ingest", "forwards", "merge"} of the last call
 _WARNED_CLASSES = False
+CANDIDATE_LEVELS = 5           # FPN levels of the ATSS head: a transform returns at most CANDIDATE_LEVELS x PRE_NMS_TOP_N candidates per image
 
 
 def get_size(image_size, size, max_size):
@@ -162,11 +171,12 @@ def class_list(cfg):
     return [int(c) for c in sel] if len(sel) else list(range(1, cfg.TEST.NUM_CLASSES))
 
 
-def merge(dets, orig_wh, cfg, device, row_cap=None, stats=None):
+def merge(dets, orig_wh, cfg, device, row_cap=None, stats=None, nms_path="auto"):
     """dets: per transform (packed [B, K, 6], counts [B], scaled (w, h) per image, flipped, range or None) in concatenation order ->
     list[BoxList] of box_aug.py's merge with TEST.SPECIAL_NMS 'none', 'soft-nms', 'vote' or 'soft-vote' (ops.tta_merge; the last three:
     mq_tta_merge_special, csrc/tta.hip).  row_cap / stats: ops.tta_merge (the LDS row cap of the special modes, and the count of classes
-    that went through the global workspace, returned as an int in stats["workspace_classes"])."""
+    that went through the global workspace, returned as an int in stats["workspace_classes"]).  nms_path ('none' only): "auto" = mq_ml_nms
+    up to ops.TTA_MERGE_MAX_ROWS rows per image and mq_tta_merge_nms beyond, "segmented" = mq_tta_merge_nms at any size; the same rows."""
     global _WARNED_CLASSES
     from . import ops
     T, B = len(dets), len(orig_wh)
@@ -194,8 +204,9 @@ def merge(dets, orig_wh, cfg, device, row_cap=None, stats=None):
                          "every member of a cluster beside the merged row, more rows than the merge has room for")
     st = {} if stats is not None else None
     boxes, scores, labels, n_out, ndrop = ops.tta_merge(packed, counts, tparam, band, torch.from_numpy(rank).to(device), float(cfg.TEST.TH),
-                                                        int(cfg.TEST.PRE_NMS_TOP_N), mode=mode, aux=aux, row_cap=row_cap, stats=st)
-    ran = st is not None and "workspace_classes" in st          # (not with 'none', nor at TEST.TH <= 0: no per-class step ran)
+                                                        int(cfg.TEST.PRE_NMS_TOP_N), mode=mode, aux=aux, row_cap=row_cap, stats=st,
+                                                        nms_path=nms_path)
+    ran = st is not None and "workspace_classes" in st          # (not with mq_ml_nms, nor at TEST.TH <= 0: no per-class step ran)
     nd = torch.cat([n_out, ndrop] + ([st["workspace_classes"]] if ran else [])).tolist()      # one read-back for all three
     if stats is not None:
         stats["workspace_classes"] = nd[2 * B] if ran else 0
@@ -213,7 +224,7 @@ def merge(dets, orig_wh, cfg, device, row_cap=None, stats=None):
     return out
 
 
-def merge_result_from_multi_scales(boxlists, cfg, row_cap=None, stats=None):
+def merge_result_from_multi_scales(boxlists, cfg, row_cap=None, stats=None, nms_path="auto"):
     """box_aug.py:166-206 under its own name: list[BoxList] (one per image: the detections of every transform, already concatenated in the
     image's original frame, fields "scores" and "labels") -> list[BoxList], merged per class by TEST.SPECIAL_NMS ('none', 'soft-nms', 'vote',
     'soft-vote') at TEST.TH and cut to TEST.PRE_NMS_TOP_N, on the device the boxes live on.  For a caller that keeps the reference's own
@@ -231,16 +242,22 @@ def merge_result_from_multi_scales(boxlists, cfg, row_cap=None, stats=None):
             packed[b, :n, 4] = bl.get_field("scores").to(device=device, dtype=torch.float32)
             packed[b, :n, 5] = bl.get_field("labels").to(device=device, dtype=torch.float32)
     wh = [tuple(bl.size) for bl in boxlists]
-    return merge([(packed, [len(bl) for bl in boxlists], wh, False, None)], wh, cfg, device, row_cap=row_cap, stats=stats)
+    return merge([(packed, [len(bl) for bl in boxlists], wh, False, None)], wh, cfg, device, row_cap=row_cap, stats=stats, nms_path=nms_path)
 
 
 def check_supported(model):
-    """Everything the call would refuse, checked before the first forward."""
+    """Everything the call would refuse, checked before the first forward.  TEST.USE_MULTISCALE (the reference's protocol: every
+    transform returns its un-suppressed candidates) lifts the refusal of the special merges and sizes the rows as transforms x levels x
+    PRE_NMS_TOP_N against the 2^24 of the per-class merges."""
     from . import ops
     cfg = model.cfg
+    candidates = bool(cfg.TEST.get("USE_MULTISCALE", False))
     nms = cfg.TEST.get("SPECIAL_NMS", "none")
-    if nms != "none":
-        raise NotImplementedError(f"TEST.SPECIAL_NMS = {nms!r} is not implemented by the device TTA merge (only 'none')")
+    if nms not in ops.TTA_SPECIAL_MODES:
+        raise ValueError(f"TEST.SPECIAL_NMS = {nms!r}: one of {sorted(ops.TTA_SPECIAL_MODES)}")
+    if nms != "none" and not candidates:
+        raise NotImplementedError(f"TEST.SPECIAL_NMS = {nms!r} is not implemented by the device TTA merge (only 'none') unless "
+                                  "TEST.USE_MULTISCALE is set: the reference runs the special merges on un-suppressed candidates only")
     if cfg.get("GROUNDINGDINO", {}).get("enabled", False):
         raise NotImplementedError("test-time augmentation (TEST.USE_MULTISCALE) is implemented for MQ-GLIP only, not MQ-GroundingDINO")
     cl = class_list(cfg)
@@ -248,8 +265,15 @@ def check_supported(model):
         # the reference would return such a class's detections once per repetition; the device merge ranks rows by class-list position
         raise NotImplementedError(f"TEST.SELECT_CLASSES repeats a class ({cl}): not supported by the device TTA merge")
     from .modeling.pipeline import TIE_SLOTS
+    transforms = len(cfg.TEST.SCALES) * (2 if cfg.TEST.FLIP else 1)
+    if candidates:
+        rows = transforms * CANDIDATE_LEVELS * int(cfg.MODEL.ATSS.PRE_NMS_TOP_N)
+        if rows > ops.TTA_MERGE_MAX_ROWS_ANY:
+            raise ValueError(f"TTA merge: {rows} candidate rows per image (transforms x {CANDIDATE_LEVELS} levels x MODEL.ATSS.PRE_NMS_TOP_N) "
+                             f"exceed the {ops.TTA_MERGE_MAX_ROWS_ANY} the merge takes: lower MODEL.ATSS.PRE_NMS_TOP_N or the number of TEST.SCALES")
+        return
     kd = int(cfg.MODEL.ATSS.DETECTIONS_PER_IMG)
-    rows = len(cfg.TEST.SCALES) * (2 if cfg.TEST.FLIP else 1) * (kd + int(cfg.MODEL.ATSS.get("TIE_SLOTS", TIE_SLOTS)))
+    rows = transforms * (kd + int(cfg.MODEL.ATSS.get("TIE_SLOTS", TIE_SLOTS)))
     if cfg.TEST.TH > 0 and kd > 0 and rows > ops.TTA_MERGE_MAX_ROWS:
         raise ValueError(f"TTA merge: {rows} detection rows per image (transforms x (DETECTIONS_PER_IMG + TIE_SLOTS)) exceed the "
                          f"{ops.TTA_MERGE_MAX_ROWS} the merge's NMS takes: lower MODEL.ATSS.DETECTIONS_PER_IMG or the number of TEST.SCALES")
@@ -257,7 +281,8 @@ def check_supported(model):
 
 @torch.no_grad()
 def im_detect_bbox_aug(model, images, device, captions=None, positive_map_label_to_token=None):
-    """box_aug.py:12-63 (SPECIAL_NMS 'none'), reading model.cfg.  images: RGB PIL images (BBoxAugCollator) or HWC uint8 tensors / arrays.
+    """box_aug.py:12-63, reading model.cfg (TEST.USE_MULTISCALE True: the reference's protocol, un-suppressed candidates from every
+    transform and any TEST.SPECIAL_NMS; False: post-NMS rows and 'none' only -- see the module docstring).  images: RGB PIL images (BBoxAugCollator) or HWC uint8 tensors / arrays.
     Every transform goes through `model(...)`, so vision-only evaluation (VISION_QUERY.MASK_DURING_INFERENCE, detector._masked_ids) applies
     to each of them with no code here."""
     check_supported(model)
