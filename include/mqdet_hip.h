@@ -299,6 +299,29 @@ typedef struct mq_fuse_level {
 int mq_dyconv_epilogue_group(const mq_fuse_level* levels, int nl, const void* w0, const void* b0, const void* w2, const void* b2,
                              int B, int C, void* stream);
 int mq_dyrelu_apply(void* x, const float* coef, int B, int n, int C, long x_bs, void* stream);
+/* mq_dyrelu_apply of every pyramid level of the token buffer x [B,N,C] (batch stride x_bs) in one launch: coef [NL][B][4][C] fp32,
+ * row_first: NL + 1 HOST ints (level l = rows [row_first[l], row_first[l+1]) of every image; NL <= 8), C % 8 == 0.  Bit-equal to the
+ * NL per-level calls.  KERNELS["DYRELU_APPLY_GROUPED"]. */
+int mq_dyrelu_apply_group(void* x, long x_bs, const float* coef, const int* row_first, int NL, int B, int N, int C, void* stream);
+/* The DyConv epilogue with DYReLU known BEFORE the fuse pass (KERNELS["DYCONV_EPILOGUE_LN"]).  The fused map is affine per channel in its
+ * branches and the third DCN statistic is the spatial mean of each (up-sampled) branch, so mean(out)[b,c] = sum_k (coef_k[b,c,0] * s2_k[b,c] +
+ * coef_k[b,c,1]) needs no pass over `out`.
+ *   mq_dyconv_coef_relu_group : mq_dyconv_coef_group (coef of every branch, bit-equal to it) AND the DYReLU coefficients of every level in
+ *     one launch, grid (B, nl).  level: nbr HOST ints, the pyramid level (0 .. nl - 1) branch i is fused into, <= 3 branches per level, summed
+ *     in host order; w0 / b0 / w2 / b2 as for mq_dyconv_epilogue_group; relu_coef [nl, B, 4, C] fp32 out.  The mean is that of the unrounded
+ *     fp32 map (mq_dyconv_epilogue_group sums the 16-bit outputs): the DYReLU coefficients agree with its to rounding, not bit for bit.
+ *   mq_dyconv_fuse_act_group  : the fuse pass of mq_dyconv_epilogue_group (same work list and arithmetic, the sum rounded to 16 bits as
+ *     there) with DYReLU applied per position from levels[i].relu_coef ([B,4,C], an INPUT here; pool is not used and may be NULL), then
+ *       mode 1: LayerNorm over the C channels with gamma / beta (16-bit [C]) and eps in the arithmetic of mq_dyrelu_ln_fwd -- `out` of the
+ *               levels are the slices of the NEXT fusion layer's LN(v) buffer; bit-equal to mq_dyconv_epilogue_group + mq_dyrelu_ln_fwd
+ *               given the same relu_coef;
+ *       mode 0: rounded to 16 bits -- bit-equal to mq_dyconv_epilogue_group + mq_dyrelu_apply given the same relu_coef (gamma / beta unused).
+ * C == 256, nl <= 8. */
+int mq_dyconv_coef_relu_group(const mq_coef_branch* branches, int nbr, const int* level, int nl, const float* attn_w, const float* attn_b,
+                              const void* w0, const void* b0, const void* w2, const void* b2, float* relu_coef, int B, int C, int G, float eps,
+                              void* stream);
+int mq_dyconv_fuse_act_group(const mq_fuse_level* levels, int nl, const void* gamma, const void* beta, float eps, int mode, int B, int C,
+                             void* stream);
 /* FPN top-down step (backbone/fpn.py:82-95) in place: dst [B,H,W,C] += nearest-up-sampled src [B,Hc,Wc,C] (NHWC 16-bit, C % 8 == 0;
  * source index = min(floor(i * (float)(in / out)), in - 1) as F.interpolate(mode="nearest", size=(H, W))). */
 int mq_add_upsample_nearest(void* dst, const void* src, int B, int H, int W, int Hc, int Wc, int C, void* stream);
@@ -635,7 +658,10 @@ MQ_BF16_TWIN(mq_dyconv_coef_group)
 MQ_BF16_TWIN(mq_dyconv_fuse)
 MQ_BF16_TWIN(mq_dyrelu_coef)
 MQ_BF16_TWIN(mq_dyconv_epilogue_group)
+MQ_BF16_TWIN(mq_dyconv_coef_relu_group)
+MQ_BF16_TWIN(mq_dyconv_fuse_act_group)
 MQ_BF16_TWIN(mq_dyrelu_apply)
+MQ_BF16_TWIN(mq_dyrelu_apply_group)
 MQ_BF16_TWIN(mq_add_upsample_nearest)
 MQ_BF16_TWIN(mq_pool2x2_tokens_fwd)
 MQ_BF16_TWIN(mq_dyrelu_ln_fwd)
@@ -697,7 +723,10 @@ MQ_F32_TWIN(mq_dyconv_coef_group)
 MQ_F32_TWIN(mq_dyconv_fuse)
 MQ_F32_TWIN(mq_dyrelu_coef)
 MQ_F32_TWIN(mq_dyconv_epilogue_group)
+MQ_F32_TWIN(mq_dyconv_coef_relu_group)
+MQ_F32_TWIN(mq_dyconv_fuse_act_group)
 MQ_F32_TWIN(mq_dyrelu_apply)
+MQ_F32_TWIN(mq_dyrelu_apply_group)
 MQ_F32_TWIN(mq_dyrelu_ln_fwd)
 MQ_F32_TWIN(mq_add_upsample_nearest)
 MQ_F32_TWIN(mq_pool2x2_tokens_fwd)

@@ -130,13 +130,19 @@ extern "C" int MQ_SYM(mq_dyconv_coef)(const float* sums, const void* gamma, cons
 struct CoefBranch { const float* part; const half_t* gamma; const half_t* beta; float* coef; int nblk, n; float inv_nbr; int pad; };
 struct CoefGroup { CoefBranch br[16]; const float* attn_w; const float* attn_b; int C, G; float eps; int nbr; };
 
-__global__ __launch_bounds__(1024) void dyconv_coef_group_kernel(CoefGroup g) {
-  __shared__ float red[4][256][3];
-  __shared__ float cs[256], css[256];
-  __shared__ float gs[64], gss[64];
-  __shared__ float dotp[256];
-  const CoefBranch br = g.br[blockIdx.y];
-  const int b = blockIdx.x, c = threadIdx.x & 255, q = threadIdx.x >> 8, C = g.C;
+// (body shared by the per-branch grid and by dyconv_coef_relu_group_kernel, which walks the branches of a level: all 1024 threads take part in
+// every barrier; the threads of reducer 0 store coef[b, c, 0..1] and get them back as c0 / c1 with sw = the weighted spatial mean of y)
+struct CoefShared {
+  float red[4][256][3];
+  float cs[256], css[256];
+  float gs[64], gss[64];
+  float dotp[256];
+};
+__device__ __forceinline__ void dyconv_coef_branch_body(const CoefBranch& br, const float* __restrict__ attn_w, const float* __restrict__ attn_b,
+                                                        int C, int G, float eps, int b, CoefShared& sm, float& c0, float& c1, float& sw) {
+  float (*red)[256][3] = sm.red;
+  float *cs = sm.cs, *css = sm.css, *gs = sm.gs, *gss = sm.gss, *dotp = sm.dotp;
+  const int c = threadIdx.x & 255, q = threadIdx.x >> 8;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   const float* base = br.part + ((long)b * br.nblk * C + c) * 3;
   // fixed order per reducer (k = q, q + 4, ...), eight partials' loads in flight at a time: one load per iteration was a chain of 36
@@ -168,8 +174,8 @@ __global__ __launch_bounds__(1024) void dyconv_coef_group_kernel(CoefGroup g) {
     cs[c] = s[0]; css[c] = s[1];
   }
   __syncthreads();
-  const int cpg = C / g.G;
-  if (threadIdx.x < g.G) {
+  const int cpg = C / G;
+  if (threadIdx.x < G) {
     float a0 = 0.f, a1 = 0.f;
     for (int j = 0; j < cpg; ++j) { a0 += cs[threadIdx.x * cpg + j]; a1 += css[threadIdx.x * cpg + j]; }
     gs[threadIdx.x] = a0; gss[threadIdx.x] = a1;
@@ -178,38 +184,49 @@ __global__ __launch_bounds__(1024) void dyconv_coef_group_kernel(CoefGroup g) {
   const float cnt = (float)br.n * cpg;
   const float mean = gs[c / cpg] / cnt;
   const float var = fmaxf(gss[c / cpg] / cnt - mean * mean, 0.f);
-  const float rstd = rsqrtf(var + g.eps);
+  const float rstd = rsqrtf(var + eps);
   const float sc = rstd * (float)br.gamma[c];
   const float sh = (float)br.beta[c] - mean * sc;
-  if (q == 0) dotp[c] = g.attn_w[c] * (sc * s[2] + sh);          // s[2] = weighted spatial mean of y
+  if (q == 0) dotp[c] = attn_w[c] * (sc * s[2] + sh);          // s[2] = weighted spatial mean of y
   __syncthreads();
   for (int o = C / 2; o > 0; o >>= 1) {
     if (threadIdx.x < o) dotp[threadIdx.x] += dotp[threadIdx.x + o];
     __syncthreads();
   }
   if (q == 0) {
-    float a = fmaxf(dotp[0] + g.attn_b[0], 0.f);
+    float a = fmaxf(dotp[0] + attn_b[0], 0.f);
     a = fminf(fmaxf(a + 3.f, 0.f), 6.f) / 6.f * br.inv_nbr;
-    br.coef[((long)b * C + c) * 2 + 0] = a * sc;
-    br.coef[((long)b * C + c) * 2 + 1] = a * sh;
+    c0 = a * sc; c1 = a * sh; sw = s[2];
+    br.coef[((long)b * C + c) * 2 + 0] = c0;
+    br.coef[((long)b * C + c) * 2 + 1] = c1;
   }
+}
+
+__global__ __launch_bounds__(1024) void dyconv_coef_group_kernel(CoefGroup g) {
+  __shared__ CoefShared sm;
+  float c0 = 0.f, c1 = 0.f, sw = 0.f;
+  dyconv_coef_branch_body(g.br[blockIdx.y], g.attn_w, g.attn_b, g.C, g.G, g.eps, blockIdx.x, sm, c0, c1, sw);
 }
 
 struct mq_coef_branch {          // mirrors include/mqdet_hip.h
   const float* sums; const void* gamma; const void* beta; float* coef; int nblk, n, nbranches, reserved;
 };
 
-extern "C" int MQ_SYM(mq_dyconv_coef_group)(const mq_coef_branch* br, int nbr, const float* attn_w, const float* attn_b, int B, int C,
-                                    int G, float eps, void* stream) {
-  if (B <= 0 || nbr <= 0) return 0;
-  if (C != 256 || G > 64 || C % G || nbr > 16) return -1;
-  CoefGroup g;
+static void coef_group_fill(CoefGroup& g, const mq_coef_branch* br, int nbr, const float* attn_w, const float* attn_b, int C, int G, float eps) {
   for (int i = 0; i < nbr; ++i) {
     g.br[i].part = br[i].sums; g.br[i].gamma = (const half_t*)br[i].gamma; g.br[i].beta = (const half_t*)br[i].beta;
     g.br[i].coef = br[i].coef; g.br[i].nblk = br[i].nblk; g.br[i].n = br[i].n; g.br[i].inv_nbr = 1.f / (float)br[i].nbranches;
     g.br[i].pad = 0;
   }
   g.attn_w = attn_w; g.attn_b = attn_b; g.C = C; g.G = G; g.eps = eps; g.nbr = nbr;
+}
+
+extern "C" int MQ_SYM(mq_dyconv_coef_group)(const mq_coef_branch* br, int nbr, const float* attn_w, const float* attn_b, int B, int C,
+                                    int G, float eps, void* stream) {
+  if (B <= 0 || nbr <= 0) return 0;
+  if (C != 256 || G > 64 || C % G || nbr > 16) return -1;
+  CoefGroup g;
+  coef_group_fill(g, br, nbr, attn_w, attn_b, C, G, eps);
   hipLaunchKernelGGL(dyconv_coef_group_kernel, dim3(B, nbr), dim3(1024), 0, (hipStream_t)stream, g);
   MQ_CHECK_LAUNCH();
   return 0;
@@ -401,32 +418,11 @@ extern "C" int MQ_SYM(mq_dyconv_fuse)(const void* y0, const float* coef0, int hs
 // ---------------------------------------------------------------------------------------------- DyReLU
 // one block (256 threads) per batch element: y = pool / n -> fc0 (C -> C/4) ReLU -> fc2 (C/4 -> 4C) -> h_sigmoid
 // coef[b, 0..3, c] = a1, b1, a2, b2  (lambda_a = 2, init_a = (1, 0), init_b = (0, 0))
-__device__ __forceinline__ void dyrelu_coef_body(const float* __restrict__ pool, int nblk, const half_t* __restrict__ w0,
-                                                 const half_t* __restrict__ b0, const half_t* __restrict__ w2,
-                                                 const half_t* __restrict__ b2, float* __restrict__ coef, int n, int C, int b,
-                                                 float* yv, float* hv, float (*part)[256]) {
+// (the two FCs on a spatial mean the caller has put into yv[0 .. C): 1024 threads, begins with the barrier that publishes yv)
+__device__ __forceinline__ void dyrelu_fc_body(const half_t* __restrict__ w0, const half_t* __restrict__ b0, const half_t* __restrict__ w2,
+                                               const half_t* __restrict__ b2, float* __restrict__ coef, int C, int b, float* yv, float* hv) {
   const int t = threadIdx.x & 255, grp = threadIdx.x >> 8;
   const int S = C / 4;                                   // C == 256, S == 64 (checked by the host wrapper)
-  // spatial mean: fixed-order sum of the per-block partials.  The P3 level has 132 of them per image: one dependent chain of 17
-  // rounds of 8 loads was 42 us (the launch sits between the fuse kernel and the next LayerNorm, on the critical path); four
-  // row groups each take a contiguous quarter (8 loads in flight each) and are combined in group order.
-  {
-    const int q = (nblk + 3) / 4, k0 = grp * q, k1 = min(nblk, k0 + q);
-    float acc0 = 0.f;
-    const float* pb = pool + (long)b * nblk * C + t;
-    int k = k0;
-    for (; k + 8 <= k1; k += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = pb[(long)(k + u) * C];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc0 += v[u];
-    }
-    for (; k < k1; ++k) acc0 += pb[(long)k * C];
-    part[grp][t] = acc0;
-  }
-  __syncthreads();
-  if (grp == 0) yv[t] = (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]) / (float)n;
   __syncthreads();
   if (grp == 0) {  // fc.0 (C -> S) + ReLU: 4 lanes per output, 16-byte weight loads, fixed-order combine
     const int o = t >> 2, q = t & 3;
@@ -459,6 +455,34 @@ __device__ __forceinline__ void dyrelu_coef_body(const float* __restrict__ pool,
   }
 }
 
+__device__ __forceinline__ void dyrelu_coef_body(const float* __restrict__ pool, int nblk, const half_t* __restrict__ w0,
+                                                 const half_t* __restrict__ b0, const half_t* __restrict__ w2,
+                                                 const half_t* __restrict__ b2, float* __restrict__ coef, int n, int C, int b,
+                                                 float* yv, float* hv, float (*part)[256]) {
+  const int t = threadIdx.x & 255, grp = threadIdx.x >> 8;
+  // spatial mean: fixed-order sum of the per-block partials.  The P3 level has 132 of them per image: one dependent chain of 17
+  // rounds of 8 loads was 42 us (the launch sits between the fuse kernel and the next LayerNorm, on the critical path); four
+  // row groups each take a contiguous quarter (8 loads in flight each) and are combined in group order.
+  {
+    const int q = (nblk + 3) / 4, k0 = grp * q, k1 = min(nblk, k0 + q);
+    float acc0 = 0.f;
+    const float* pb = pool + (long)b * nblk * C + t;
+    int k = k0;
+    for (; k + 8 <= k1; k += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = pb[(long)(k + u) * C];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc0 += v[u];
+    }
+    for (; k < k1; ++k) acc0 += pb[(long)k * C];
+    part[grp][t] = acc0;
+  }
+  __syncthreads();
+  if (grp == 0) yv[t] = (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]) / (float)n;
+  dyrelu_fc_body(w0, b0, w2, b2, coef, C, b, yv, hv);
+}
+
 __global__ __launch_bounds__(1024) void dyrelu_coef_kernel(const float* __restrict__ pool, int nblk,
                                                            const half_t* __restrict__ w0,
                                                            const half_t* __restrict__ b0, const half_t* __restrict__ w2,
@@ -487,15 +511,8 @@ struct mq_fuse_level {          // mirrors include/mqdet_hip.h
   void* out; long out_bs; float* pool; float* relu_coef;
 };
 
-// The epilogue of a DyConv layer for all pyramid levels in two launches: mq_dyconv_fuse of every level (one work list), then
-// mq_dyrelu_coef of every level.  levels[i]: the arguments of those two entry points (pool [B, ceil(H*W/128), C] workspace,
-// relu_coef [B,4,C] out).  C == 256, <= 8 levels.
-extern "C" int MQ_SYM(mq_dyconv_epilogue_group)(const mq_fuse_level* levels, int nl, const void* w0, const void* b0, const void* w2,
-                                                const void* b2, int B, int C, void* stream) {
-  if (B <= 0 || nl <= 0) return 0;
-  if (C != 256 || nl > FUSE_MAX_LEVELS) return -1;
-  FuseGroup g;
-  ReluGroup r;
+// the work list of the grouped fuse kernels: the 128-position blocks of every level, the branch mix of a level picks the body
+static int fuse_group_fill(FuseGroup& g, const mq_fuse_level* levels, int nl, int B, int C) {
   g.n = 0;
   g.first_block[0] = 0;
   for (int i = 0; i < nl; ++i) {
@@ -508,17 +525,292 @@ extern "C" int MQ_SYM(mq_dyconv_epilogue_group)(const mq_fuse_level* levels, int
     g.kind[g.n] = 2 * nd + nbil;
     g.nblk[g.n] = (a.H * a.W + 127) / 128;
     g.first_block[g.n + 1] = g.first_block[g.n] + B * g.nblk[g.n];
-    r.pool[g.n] = a.pool; r.coef[g.n] = a.relu_coef; r.nblk[g.n] = g.nblk[g.n]; r.n[g.n] = a.H * a.W;
     ++g.n;
   }
   for (int i = g.n; i < FUSE_MAX_LEVELS; ++i) {
     g.lv[i] = g.lv[0]; g.nblk[i] = g.nblk[0]; g.kind[i] = g.kind[0]; g.first_block[i + 1] = g.first_block[g.n];
-    r.pool[i] = r.pool[0]; r.coef[i] = r.coef[0]; r.nblk[i] = r.nblk[0]; r.n[i] = r.n[0];
+  }
+  return 0;
+}
+
+// The epilogue of a DyConv layer for all pyramid levels in two launches: mq_dyconv_fuse of every level (one work list), then
+// mq_dyrelu_coef of every level.  levels[i]: the arguments of those two entry points (pool [B, ceil(H*W/128), C] workspace,
+// relu_coef [B,4,C] out).  C == 256, <= 8 levels.
+extern "C" int MQ_SYM(mq_dyconv_epilogue_group)(const mq_fuse_level* levels, int nl, const void* w0, const void* b0, const void* w2,
+                                                const void* b2, int B, int C, void* stream) {
+  if (B <= 0 || nl <= 0) return 0;
+  if (C != 256 || nl > FUSE_MAX_LEVELS) return -1;
+  FuseGroup g;
+  ReluGroup r;
+  if (int rc = fuse_group_fill(g, levels, nl, B, C)) return rc;
+  for (int i = 0; i < FUSE_MAX_LEVELS; ++i) {
+    const mq_fuse_level& a = levels[i < nl ? i : 0];
+    r.pool[i] = a.pool; r.coef[i] = a.relu_coef; r.nblk[i] = g.nblk[i]; r.n[i] = a.H * a.W;
   }
   r.w0 = (const half_t*)w0; r.b0 = (const half_t*)b0; r.w2 = (const half_t*)w2; r.b2 = (const half_t*)b2; r.C = C;
   hipLaunchKernelGGL(dyconv_fuse_group_kernel, dim3((unsigned)g.first_block[g.n]), dim3(256), 0, (hipStream_t)stream, g);
   MQ_CHECK_LAUNCH();
   hipLaunchKernelGGL(dyrelu_coef_group_kernel, dim3(B, g.n), dim3(1024), 0, (hipStream_t)stream, r);
+  MQ_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- DYReLU from the DCN statistics
+// The fused map is affine per channel in its branches,  out = sum_k A_k y^_k + sum_k B_k,  and the third DCN statistic IS the spatial mean
+// of y^_k (the weighted sum that dyconv_coef already feeds to the scale attention), so  mean(out)[b, c] = sum_k (A_k s2_k + B_k)  needs no
+// pass over `out`: the DYReLU coefficients are known BEFORE the fuse pass, which can then apply DYReLU (and the next LayerNorm) itself.
+// One workgroup per (image, level): the level's <= 3 branches in host order through dyconv_coef_branch_body (coef bit-equal to
+// mq_dyconv_coef_group), the mean summed in that order by the thread that owns the channel, then dyrelu_fc_body.  No atomics.
+// (The mean is that of the UNROUNDED fp32 map; the pooled path sums the 16-bit outputs -- the coefficients agree to rounding, not bitwise.)
+struct CoefReluGroup {
+  CoefGroup c;
+  int lv_br[FUSE_MAX_LEVELS][3], lv_n[FUSE_MAX_LEVELS];          // branch indices of a level, host order
+  const half_t* w0; const half_t* b0; const half_t* w2; const half_t* b2;
+  float* relu_coef;                                               // [levels, B, 4, C]
+};
+__global__ __launch_bounds__(1024) void dyconv_coef_relu_group_kernel(CoefReluGroup g) {
+  __shared__ CoefShared sm;
+  __shared__ float yv[256], hv[64];
+  const int b = blockIdx.x, L = blockIdx.y, C = g.c.C;
+  float mo = 0.f;
+  for (int i = 0; i < g.lv_n[L]; ++i) {                           // uniform over the workgroup: every thread meets every barrier
+    float c0 = 0.f, c1 = 0.f, sw = 0.f;
+    dyconv_coef_branch_body(g.c.br[g.lv_br[L][i]], g.c.attn_w, g.c.attn_b, C, g.c.G, g.c.eps, b, sm, c0, c1, sw);
+    mo += c0 * sw + c1;
+  }
+  if (threadIdx.x < 256) yv[threadIdx.x] = mo;
+  dyrelu_fc_body(g.w0, g.b0, g.w2, g.b2, g.relu_coef + (long)L * gridDim.x * 4 * C, C, b, yv, hv);
+}
+
+// level[i]: pyramid level (0 .. nl - 1) branch i is fused into; <= 3 branches per level.  relu_coef [nl, B, 4, C].
+extern "C" int MQ_SYM(mq_dyconv_coef_relu_group)(const mq_coef_branch* br, int nbr, const int* level, int nl, const float* attn_w,
+                                                 const float* attn_b, const void* w0, const void* b0, const void* w2, const void* b2,
+                                                 float* relu_coef, int B, int C, int G, float eps, void* stream) {
+  if (B <= 0 || nbr <= 0 || nl <= 0) return 0;
+  if (C != 256 || G > 64 || C % G || nbr > 16 || nl > FUSE_MAX_LEVELS) return -1;
+  CoefReluGroup g;
+  coef_group_fill(g.c, br, nbr, attn_w, attn_b, C, G, eps);
+  for (int l = 0; l < FUSE_MAX_LEVELS; ++l) { g.lv_n[l] = 0; g.lv_br[l][0] = g.lv_br[l][1] = g.lv_br[l][2] = 0; }
+  for (int i = 0; i < nbr; ++i) {
+    const int l = level[i];
+    if (l < 0 || l >= nl || g.lv_n[l] >= 3) return -1;
+    g.lv_br[l][g.lv_n[l]++] = i;
+  }
+  for (int l = 0; l < nl; ++l)
+    if (g.lv_n[l] == 0) return -1;
+  g.w0 = (const half_t*)w0; g.b0 = (const half_t*)b0; g.w2 = (const half_t*)w2; g.b2 = (const half_t*)b2; g.relu_coef = relu_coef;
+  hipLaunchKernelGGL(dyconv_coef_relu_group_kernel, dim3(B, nl), dim3(1024), 0, (hipStream_t)stream, g);
+  MQ_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- fuse + DYReLU (+ LayerNorm)
+// The fuse pass of dyconv_fuse_group_kernel (same work list, same per-position arithmetic, `o` rounded to 16 bits as there) followed, per
+// position, by DYReLU with the level's relu_coef and then
+//   MODE 1: the NEXT fusion layer's layer_norm_v, arithmetic of dyrelu_ln_kernel (fp32 f, mean, centred squares, the same 32-lane exchange
+//           order, one rounding) -> v_ln; the pre-LayerNorm buffer is never written or read;
+//   MODE 0: f rounded to 16 bits = fuse followed by mq_dyrelu_apply.
+// A position's 256 channels sit in 32 consecutive lanes x 8 channels in both kernels, so the LayerNorm needs no change of layout.  No pool
+// partials, no LDS reduction.  The trip count of the position loop is the same for every thread of the workgroup (loads clamped, stores guarded):
+// the lane exchanges run in uniform control flow.
+struct FuseActGroup {
+  FuseGroup f;
+  const float* relu[FUSE_MAX_LEVELS];          // [B, 4, C] per level
+  const half_t* gamma; const half_t* beta;     // MODE 1
+  float eps;
+};
+
+// The bilinear sample of dyconv_fuse_body, (1 - ly) ((1 - lx) v0 + lx v1) + ly ((1 - lx) v2 + lx v3), with its contraction spelled out.  Left to the
+// compiler, WHICH product of each sum joins the fma is decided per kernel (operand order after vectorisation; the first device run of the body
+// below differed from dyconv_fuse_group_kernel in the last bit of `o`).  This is the form hipcc gives the plain expression in dyconv_fuse_kernel
+// and dyconv_fuse_group_kernel, in all three builds (their IR: 2 x fma(1 - w, ., w * .) and 1 x fma(w, ., (1 - w) * .) per sample).
+// The same holds for every sum of products below (with two direct branches hipcc vectorised the products of mode LN into v_pk_mul_f32 and
+// added them unfused, while dyconv_fuse_group_kernel and mode ReLU chain fmas): the body is compiled with contraction off and says fuse_fma
+// where the kernels it must equal -- dyconv_fuse_group_kernel, dyrelu_apply_kernel, dyrelu_ln_kernel -- have an fma.
+// (The kernel-source emulation compiles all of them for a host without fused multiply-add: plain expressions there.)
+__device__ __forceinline__ float fuse_fma(float a, float b, float c) {
+#if defined(MQ_SIMT_EMULATION)
+  return a * b + c;
+#else
+  return __builtin_fmaf(a, b, c);
+#endif
+}
+__device__ __forceinline__ float fuse_bilerp(float ly, float lx, float v0, float v1, float v2, float v3) {
+#if defined(MQ_SIMT_EMULATION)
+  return (1.f - ly) * ((1.f - lx) * v0 + lx * v1) + ly * ((1.f - lx) * v2 + lx * v3);
+#else
+#pragma clang fp contract(off)
+  const float t0 = __builtin_fmaf(lx, v1, (1.f - lx) * v0);
+  const float t1 = __builtin_fmaf(1.f - lx, v2, lx * v3);
+  return __builtin_fmaf(1.f - ly, t0, ly * t1);
+#endif
+}
+
+#define MQ_PIN(x) asm volatile("" : "+v"(x))
+template <int ND, bool HB, int U, int MODE>
+__device__ __forceinline__ void dyconv_fuse_act_body(const FuseParams& p, const float* __restrict__ relu, const half_t* __restrict__ gamma,
+                                                     const half_t* __restrict__ beta, float eps, int b, int blk, float* ops) {
+  constexpr int NBR = ND + (HB ? 1 : 0), C = 256, NRG = 8;
+  const int lane_c = threadIdx.x & 31, rg = threadIdx.x >> 5;
+  const int c0 = lane_c * 8;
+  const int n = p.H * p.W;
+  const int p0 = blk * p.rows_per_block, p1 = min(n, p0 + p.rows_per_block);
+  float A[NBR][8], Bc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) Bc[j] = 0.f;
+#pragma unroll
+  for (int k = 0; k < NBR; ++k) {
+    const float* cf = p.br[k].coef + ((long)b * C + c0) * 2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { A[k][j] = cf[j * 2]; Bc[j] += cf[j * 2 + 1]; }
+  }
+  const half_t* yd[ND > 0 ? ND : 1];
+#pragma unroll
+  for (int k = 0; k < ND; ++k) yd[k] = p.br[k].y + (long)b * n * C + c0;
+  const FuseBranch& bb = p.br[NBR - 1];
+  const half_t* yb = HB ? bb.y + (long)b * bb.hs * bb.ws * C + c0 : nullptr;
+  // DYReLU coefficients (and gamma / beta as floats) of this level and image: [4 or 6][C] in LDS, one channel per thread
+  {
+    const float* cf = relu + (long)b * 4 * C;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ops[k * C + threadIdx.x] = cf[k * C + threadIdx.x];
+    if constexpr (MODE == 1) { ops[4 * C + threadIdx.x] = (float)gamma[threadIdx.x]; ops[5 * C + threadIdx.x] = (float)beta[threadIdx.x]; }
+  }
+  half_t* po = p.out + (long)b * p.out_bs + c0;
+#pragma unroll 1
+  for (int i0 = 0; p0 + NRG * i0 < p1; i0 += U) {
+    half8 vd[U][ND > 0 ? ND : 1], vb[U][4];
+    float ly[U], lx[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (p0 + NRG * (i0 + u) >= p1) break;                 // (U = 3 does not divide the 16 rounds of a block) uniform over the workgroup
+      const int pos = min(p0 + rg + NRG * (i0 + u), p1 - 1);
+#pragma unroll
+      for (int k = 0; k < ND; ++k) vd[u][k] = *(const half8*)(yd[k] + (long)pos * C);
+      if constexpr (HB) {
+        const int oy = pos / p.W, ox = pos - oy * p.W;
+        const float sy = p.H > 1 ? (float)oy * (float)(bb.hs - 1) / (float)(p.H - 1) : 0.f;
+        const float sx = p.W > 1 ? (float)ox * (float)(bb.ws - 1) / (float)(p.W - 1) : 0.f;
+        const int y0 = min((int)sy, bb.hs - 1), x0 = min((int)sx, bb.ws - 1);
+        const int y1 = min(y0 + 1, bb.hs - 1), x1 = min(x0 + 1, bb.ws - 1);
+        ly[u] = sy - (float)y0; lx[u] = sx - (float)x0;
+        vb[u][0] = *(const half8*)(yb + ((long)y0 * bb.ws + x0) * C);
+        vb[u][1] = *(const half8*)(yb + ((long)y0 * bb.ws + x1) * C);
+        vb[u][2] = *(const half8*)(yb + ((long)y1 * bb.ws + x0) * C);
+        vb[u][3] = *(const half8*)(yb + ((long)y1 * bb.ws + x1) * C);
+      }
+    }
+    if (i0 == 0) __syncthreads();                           // the operands in LDS, behind the first loads
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma clang fp contract(off)
+      if (p0 + NRG * (i0 + u) >= p1) break;
+      const int pos = p0 + rg + NRG * (i0 + u);
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = Bc[j];
+#pragma unroll
+      for (int k = 0; k < ND; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = fuse_fma(A[k][j], (float)vd[u][k][j], acc[j]);
+      if constexpr (HB) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float v = fuse_bilerp(ly[u], lx[u], (float)vb[u][0][j], (float)vb[u][1][j], (float)vb[u][2][j], (float)vb[u][3][j]);
+          acc[j] = fuse_fma(A[NBR - 1][j], v, acc[j]);
+        }
+      }
+      int co = c0;
+      MQ_PIN(co);                                             // read per position: hoisted, the 48 operands spilled 101 registers
+      float f[8];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4_ a1 = *(const float4_*)(ops + co + 4 * h), b1 = *(const float4_*)(ops + C + co + 4 * h);
+        const float4_ a2 = *(const float4_*)(ops + 2 * C + co + 4 * h), b2 = *(const float4_*)(ops + 3 * C + co + 4 * h);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          // `o` of the fuse pass: the fp32 sum, THEN rounded (pinned: hipcc otherwise folds the rounding into the last fma -- v_fma_mixlo_f16,
+          // one rounding instead of two -- and one `o` in 10^4 differs from dyconv_fuse_group_kernel's in the last bit)
+          MQ_PIN(acc[4 * h + j]);
+          const float x = (float)(half_t)acc[4 * h + j];
+          f[4 * h + j] = fmaxf(fuse_fma(x, a1[j], b1[j]), fuse_fma(x, a2[j], b2[j]));
+        }
+      }
+      half8 o;
+      if constexpr (MODE == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (half_t)f[j];
+      } else {
+        float g[8], bt[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float4_ t0 = *(const float4_*)(ops + 4 * C + co + 4 * h), t1 = *(const float4_*)(ops + 5 * C + co + 4 * h);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { g[4 * h + j] = t0[j]; bt[4 * h + j] = t1[j]; }
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += f[j];
+#pragma unroll
+        for (int m = 1; m < 32; m <<= 1) s += __shfl_xor(s, m);
+        const float mean = s / (float)C;
+        float q = 0.f;
+        // (squares rounded, then added: hipcc vectorises the squares of dyrelu_ln_kernel -- v_pk_mul_f32 -- and adds them one by one, in all three builds)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float d = f[j] - mean; q += d * d; }
+#pragma unroll
+        for (int m = 1; m < 32; m <<= 1) q += __shfl_xor(q, m);
+        const float rstd = rsqrtf(q / (float)C + eps);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float r = fuse_fma((f[j] - mean) * rstd, g[j], bt[j]);
+          MQ_PIN(r);                                          // fp32 result, then rounded, as dyrelu_ln_kernel's
+          o[j] = (half_t)r;
+        }
+      }
+      if (pos < p1) *(half8*)(po + (long)pos * C) = o;
+      __builtin_amdgcn_sched_barrier(0);                      // one position at a time: interleaved, their operands and sums spill
+    }
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256, MQ_FUSE_GROUP_WAVES) void dyconv_fuse_act_group_kernel(FuseActGroup g) {
+  __shared__ float ops[(MODE == 1 ? 6 : 4) * 256];
+  int L = 0;
+  while (L + 1 < g.f.n && (int)blockIdx.x >= g.f.first_block[L + 1]) ++L;
+  const FuseParams& p = g.f.lv[L];
+  const int t = blockIdx.x - g.f.first_block[L], nblk = g.f.nblk[L];
+  const int b = t / nblk, blk = t - b * nblk;
+  const float* relu = g.relu[L];
+  switch (g.f.kind[L]) {
+    case 2: dyconv_fuse_act_body<1, false, 4, MODE>(p, relu, g.gamma, g.beta, g.eps, b, blk, ops); break;
+    case 4: dyconv_fuse_act_body<2, false, 4, MODE>(p, relu, g.gamma, g.beta, g.eps, b, blk, ops); break;
+    case 6: dyconv_fuse_act_body<3, false, 4, MODE>(p, relu, g.gamma, g.beta, g.eps, b, blk, ops); break;
+    case 1: dyconv_fuse_act_body<0, true, 4, MODE>(p, relu, g.gamma, g.beta, g.eps, b, blk, ops); break;
+    // (one position fewer in flight than the bodies of dyconv_fuse_group_kernel where a bilinear branch is read: with U = 4 / 3 the DYReLU and
+    // LayerNorm temporaries spilled 14 .. 29 registers at three waves per SIMD)
+    case 3: dyconv_fuse_act_body<1, true, 3, MODE>(p, relu, g.gamma, g.beta, g.eps, b, blk, ops); break;
+    default: dyconv_fuse_act_body<2, true, 2, MODE>(p, relu, g.gamma, g.beta, g.eps, b, blk, ops); break;
+  }
+}
+
+// levels: as for mq_dyconv_epilogue_group, with relu_coef [B,4,C] an INPUT (mq_dyconv_coef_relu_group) and pool unused (may be NULL).
+// mode 1: out = LayerNorm_{gamma, beta, eps}(DYReLU(fused)) -- the levels' `out` are slices of the next layer's v_ln; mode 0: out = DYReLU(fused).
+extern "C" int MQ_SYM(mq_dyconv_fuse_act_group)(const mq_fuse_level* levels, int nl, const void* gamma, const void* beta, float eps, int mode,
+                                                int B, int C, void* stream) {
+  if (B <= 0 || nl <= 0) return 0;
+  if (C != 256 || nl > FUSE_MAX_LEVELS || (mode != 0 && mode != 1) || (mode == 1 && (!gamma || !beta))) return -1;
+  FuseActGroup g;
+  if (int rc = fuse_group_fill(g.f, levels, nl, B, C)) return rc;
+  for (int i = 0; i < FUSE_MAX_LEVELS; ++i) {
+    g.relu[i] = levels[i < nl ? i : 0].relu_coef;
+    if (!g.relu[i]) return -1;
+  }
+  g.gamma = (const half_t*)gamma; g.beta = (const half_t*)beta; g.eps = eps;
+  const dim3 grid((unsigned)g.f.first_block[g.f.n]);
+  if (mode == 1) hipLaunchKernelGGL(dyconv_fuse_act_group_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, g);
+  else hipLaunchKernelGGL(dyconv_fuse_act_group_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, g);
   MQ_CHECK_LAUNCH();
   return 0;
 }
@@ -561,6 +853,57 @@ extern "C" int MQ_SYM(mq_dyrelu_apply)(void* x, const float* coef, int B, int n,
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(dyrelu_apply_kernel, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, (half_t*)x, coef,
                      (long)n, C, x_bs);
+  MQ_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- mq_dyrelu_apply_group: mq_dyrelu_apply of EVERY pyramid level of the token buffer x [B, N, C] in one launch (the last DyConv layer:
+// were NL launches on NL streams behind a fork / join of the captured graph).  coef [NL][B][4][C] fp32, level l = rows [row_first[l],
+// row_first[l + 1]) of every image.  The per-element expression is dyrelu_apply_kernel's, so the results are its bits.
+struct ReluApplyGroup {
+  half_t* x; const float* coef;
+  long x_bs;
+  int B, N, C, NL;
+  int row_first[9];
+};
+
+__global__ __launch_bounds__(256) void dyrelu_apply_group_kernel(ReluApplyGroup g) {
+  const int b = blockIdx.y;
+  const int C = g.C, cpt = C / 8;
+  const long total = (long)g.N * cpt;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int c0 = (int)(i % cpt) * 8;
+    const int row = (int)(i / cpt);
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) l += (k < g.NL && row >= g.row_first[k]) ? 1 : 0;       // row_first ascends: the level that holds `row`
+    const float* cf = g.coef + ((long)l * g.B + b) * 4 * C;
+    half_t* px = g.x + (long)b * g.x_bs + (long)row * C + c0;
+    half8 v = *(const half8*)px;
+    half8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float f = (float)v[j];
+      o[j] = (half_t)fmaxf(f * cf[c0 + j] + cf[C + c0 + j], f * cf[2 * C + c0 + j] + cf[3 * C + c0 + j]);
+    }
+    *(half8*)px = o;
+  }
+}
+
+// row_first: NL + 1 host ints (row_first[0] = 0, row_first[NL] = N), NL <= 8, C % 8 == 0.
+extern "C" int MQ_SYM(mq_dyrelu_apply_group)(void* x, long x_bs, const float* coef, const int* row_first, int NL, int B, int N, int C,
+                                             void* stream) {
+  if (B <= 0 || N <= 0) return 0;
+  if (C % 8 || NL < 1 || NL > 8 || row_first[0] != 0 || row_first[NL] != N) return -1;
+  ReluApplyGroup g;
+  g.x = (half_t*)x; g.coef = coef; g.x_bs = x_bs; g.B = B; g.N = N; g.C = C; g.NL = NL;
+  for (int l = 0; l <= 8; ++l) {
+    g.row_first[l] = l <= NL ? row_first[l] : N;
+    if (l > 0 && l <= NL && row_first[l] <= row_first[l - 1]) return -1;
+  }
+  long blocks = ((long)N * (C / 8) + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(dyrelu_apply_group_kernel, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, g);
   MQ_CHECK_LAUNCH();
   return 0;
 }

@@ -729,28 +729,12 @@ def _upsample_pool_weights(hs, ws, H, W, device):
     return _UP_W[key]
 
 
-def dyconv_tokens(P, cfg, b, tok, sizes, defer_relu=False):
-    """DyConv.forward (vldyhead.py:205-247) on the pyramid token buffer tok [B, N, 256] -> new buffer of the same shape.
-      1. per level: 27-channel offset / mask conv (LDS-window kernel)                       -- five streams
-      2. ALL DCNv2 branches of the layer (3 per level, 13 in total) in ONE grouped launch (dcn_fused.hip): gather + bilinear
-         blend + MFMA + GroupNorm statistics; offsets of the CURRENT level are re-used for the level's three branches exactly
-         like the reference (flat-index quirk handled inside the gather)
-      3. per level: the fused HIP epilogue (GroupNorm affine, bilinear up-sampling of the level+1 branch, scale attention,
-         branch mean, DYReLU) written straight into the level's slice of the output buffer     -- five streams
-    defer_relu: return (buffer BEFORE DYReLU, coef [NL, B, 4, C]) -- the caller's next LayerNorm applies it (ops.dyrelu_layer_norm)."""
-    G = cfg.MODEL.GROUP_NORM
-    nl = len(sizes)
-    Bn, N, C = tok.shape
-    offs = [0]
-    for (hh, ww) in sizes:
-        offs.append(offs[-1] + hh * ww)
-    lv = [tok[:, offs[l]:offs[l + 1]].reshape(Bn, sizes[l][0], sizes[l][1], C) for l in range(nl)]      # NHWC views
-    out = torch.empty_like(tok)
+def _level_fan_out(cfg, tok, nl):
+    """-> fan_out(fn): fn(level) for every level: the big level (75 % of the positions) on the main stream, the others on side streams
+    (inside the HIP-graph capture: parallel graph branches); P5-P7 alone cannot fill 256 CUs."""
     streams = bool(cfg.MODEL.DYHEAD.get("LEVEL_STREAMS", True) and tok.is_cuda and nl > 1)
 
     def fan_out(fn):
-        """fn(level) for every level: the big level (75 % of the positions) on the main stream, the others on side streams
-        (inside the HIP-graph capture: parallel graph branches); P5-P7 alone cannot fill 256 CUs."""
         if not streams:
             for l in range(nl):
                 fn(l)
@@ -765,7 +749,18 @@ def dyconv_tokens(P, cfg, b, tok, sizes, defer_relu=False):
         fn(0)
         for s_ in side:
             main.wait_stream(s_)
+    return fan_out
 
+
+def _dyconv_dcn(P, b, tok, sizes, fan_out):
+    """Steps 1 and 2 of dyconv_tokens: the offset / mask conv of every level and ALL DCNv2 branches of the layer in one grouped launch.
+    -> (offs: first token of every level, owner: (level, k, branches of the level) per branch, ys: ops.dcnv2_group's (y, (Ho, Wo), sums))"""
+    nl = len(sizes)
+    Bn, N, C = tok.shape
+    offs = [0]
+    for (hh, ww) in sizes:
+        offs.append(offs[-1] + hh * ww)
+    lv = [tok[:, offs[l]:offs[l + 1]].reshape(Bn, sizes[l][0], sizes[l][1], C) for l in range(nl)]      # NHWC views
     om = [None] * nl
 
     def offsets(lvl):
@@ -792,7 +787,24 @@ def dyconv_tokens(P, cfg, b, tok, sizes, defer_relu=False):
             branches.append({"x": x_nhwc, "om": om[lvl], "w": _dcn_w(P, f"{b}.DyConv.{k}"), "bias": P[f"{b}.DyConv.{k}.conv.bias"],
                              "stride": stride, "wy": wy, "wx": wx})
             owner.append((lvl, k, len(spec)))
-    ys = ops.dcnv2_group(branches, want_stats=True)
+    return offs, owner, ops.dcnv2_group(branches, want_stats=True)
+
+
+def dyconv_tokens(P, cfg, b, tok, sizes, defer_relu=False):
+    """DyConv.forward (vldyhead.py:205-247) on the pyramid token buffer tok [B, N, 256] -> new buffer of the same shape.
+      1. per level: 27-channel offset / mask conv (LDS-window kernel)                       -- five streams
+      2. ALL DCNv2 branches of the layer (3 per level, 13 in total) in ONE grouped launch (dcn_fused.hip): gather + bilinear
+         blend + MFMA + GroupNorm statistics; offsets of the CURRENT level are re-used for the level's three branches exactly
+         like the reference (flat-index quirk handled inside the gather)
+      3. per level: the fused HIP epilogue (GroupNorm affine, bilinear up-sampling of the level+1 branch, scale attention,
+         branch mean, DYReLU) written straight into the level's slice of the output buffer     -- five streams
+    defer_relu: return (buffer BEFORE DYReLU, coef [NL, B, 4, C]) -- the caller's next LayerNorm applies it (ops.dyrelu_layer_norm)."""
+    G = cfg.MODEL.GROUP_NORM
+    nl = len(sizes)
+    Bn, N, C = tok.shape
+    out = torch.empty_like(tok)
+    fan_out = _level_fan_out(cfg, tok, nl)
+    offs, owner, ys = _dyconv_dcn(P, b, tok, sizes, fan_out)
     # GroupNorm affine x scale attention of every branch, one launch (the statistics came out of the DCN epilogue)
     coefs = ops.dyconv_coef_group(
         [{"sums": sums, "n": Ho * Wo, "gamma": P[f"{b}.DyConv.{k}.bn.weight"], "beta": P[f"{b}.DyConv.{k}.bn.bias"], "nbranches": nb}
@@ -817,11 +829,32 @@ def dyconv_tokens(P, cfg, b, tok, sizes, defer_relu=False):
         ops.dyconv_epilogue_group(
             [([(y, coef, Ho, Wo) for (l2, k, nb), (y, (Ho, Wo), sums), coef in zip(owner, ys, coefs) if l2 == lvl], sizes[lvl][0], sizes[lvl][1],
               out[:, offs[lvl]:offs[lvl + 1]]) for lvl in range(nl)], *rw, rc)
-        if not defer_relu:
+        if not defer_relu and ops.KERNELS.get("DYRELU_APPLY_GROUPED", 0) == 1 and tok.is_cuda and hasattr(ops, "dyrelu_apply_group_"):
+            ops.dyrelu_apply_group_(out, rc, sizes)       # every level in one launch on this stream, no fork / join: the same bits
+        elif not defer_relu:
             fan_out(lambda lvl: ops.dyrelu_apply_(out[:, offs[lvl]:offs[lvl + 1]], rc[lvl]))
     else:
         fan_out(epilogue)
     return (out, relu_coef) if defer_relu else out
+
+
+def dyconv_tokens_act(P, cfg, b, tok, sizes, ln=None):
+    """dyconv_tokens with the DYReLU coefficients taken from the DCN statistics (ops.dyconv_coef_relu_group: the spatial mean of the fused map
+    is sum_k A_k s2_k + B_k) and DYReLU applied by the fuse pass itself (ops.dyconv_fuse_act_group) -- KERNELS["DYCONV_EPILOGUE_LN"]; C == 256,
+    <= 8 levels.  ln = (gamma, beta, eps) of the NEXT fusion layer's layer_norm_v: -> LN(DYReLU(dyconv(tok))), that layer's v_ln (the buffer in
+    between is never written); ln None (last layer): -> DYReLU(dyconv(tok)), the finished token buffer, no per-level launches."""
+    G = cfg.MODEL.GROUP_NORM
+    nl = len(sizes)
+    offs, owner, ys = _dyconv_dcn(P, b, tok, sizes, _level_fan_out(cfg, tok, nl))
+    coefs, relu_coef = ops.dyconv_coef_relu_group(
+        [{"sums": sums, "n": Ho * Wo, "gamma": P[f"{b}.DyConv.{k}.bn.weight"], "beta": P[f"{b}.DyConv.{k}.bn.bias"], "nbranches": nb, "level": lvl}
+         for (lvl, k, nb), (y, (Ho, Wo), sums) in zip(owner, ys)], P[b + ".attn_w"], P[b + ".attn_b"], G.NUM_GROUPS, G.EPSILON,
+        P[b + ".relu.fc.0.weight"], P[b + ".relu.fc.0.bias"], P[b + ".relu.fc.2.weight"], P[b + ".relu.fc.2.bias"], nl)
+    out = torch.empty_like(tok)
+    ops.dyconv_fuse_act_group(
+        [([(y, coef, Ho, Wo) for (l2, k, nb), (y, (Ho, Wo), sums), coef in zip(owner, ys, coefs) if l2 == lvl], sizes[lvl][0], sizes[lvl][1],
+          out[:, offs[lvl]:offs[lvl + 1]]) for lvl in range(nl)], relu_coef, *(ln if ln is not None else (None, None, 1e-5)))
+    return out
 
 
 def dyconv(P, cfg, b, feats):
@@ -876,6 +909,12 @@ def vldyhead(P, cfg, feats, lang, trace=None):
     # every layer's output: a trace run applies it to a COPY for the record and still takes the deferred path itself)
     defer = ops.KERNELS["DYRELU_IN_LN"] == 1 and tok.shape[-1] == 256 and len(sizes) <= 8
     relu_coef = None
+    # ... and with KERNELS["DYCONV_EPILOGUE_LN"] by the DyConv fuse pass itself, together with that LayerNorm (dyconv_tokens_act): layer i hands
+    # v_ln of layer i + 1 over, the last layer the finished buffer.  Device only, not under a trace (the ladder records every layer's buffer), and
+    # only with an ops namespace that has the two wrappers (the plain-torch stand-in of the CPU pipeline tests keeps the calls above)
+    fuse_act = (defer and ops.KERNELS.get("DYCONV_EPILOGUE_LN", 0) == 1 and ops.KERNELS["DYCONV_EPILOGUE_GROUPED"] == 1 and tok.is_cuda and trace is None
+                and hasattr(ops, "dyconv_coef_relu_group") and hasattr(ops, "dyconv_fuse_act_group"))
+    v_next = None
 
     def relu_applied_copy():
         if relu_coef is None:
@@ -887,14 +926,22 @@ def vldyhead(P, cfg, feats, lang, trace=None):
         return cp
 
     def norm_v(b):
+        if v_next is not None:
+            return v_next
         if relu_coef is not None:
             return ops.dyrelu_layer_norm(tok, relu_coef, sizes, P[b + ".layer_norm_v.weight"], P[b + ".layer_norm_v.bias"], 1e-5)
         return ops.layer_norm(tok, P[b + ".layer_norm_v.weight"], P[b + ".layer_norm_v.bias"], 1e-5)
 
     def dyconv_layer(i):
+        """-> (token buffer, deferred DYReLU coefficients or None, v_ln of the next fusion layer or None)"""
+        if fuse_act and i + 1 < L:
+            nb = f"{t}.{3 * (i + 1)}.b_attn"
+            return tok, None, dyconv_tokens_act(P, cfg, f"{t}.{3 * i + 2}", tok, sizes, ln=(P[nb + ".layer_norm_v.weight"], P[nb + ".layer_norm_v.bias"], 1e-5))
+        if fuse_act:
+            return dyconv_tokens_act(P, cfg, f"{t}.{3 * i + 2}", tok, sizes), None, None
         if defer and i + 1 < L:
-            return dyconv_tokens(P, cfg, f"{t}.{3 * i + 2}", tok, sizes, defer_relu=True)
-        return dyconv_tokens(P, cfg, f"{t}.{3 * i + 2}", tok, sizes), None
+            return (*dyconv_tokens(P, cfg, f"{t}.{3 * i + 2}", tok, sizes, defer_relu=True), None)
+        return dyconv_tokens(P, cfg, f"{t}.{3 * i + 2}", tok, sizes), None, None
 
     if not two_streams:
         for i in range(L):
@@ -905,7 +952,7 @@ def vldyhead(P, cfg, feats, lang, trace=None):
             hidden, h32 = text_side(b, v_ln, prep)
             rec = {"fuse_tok": tok, "fuse_hidden": hidden if h32 is None else h32}
             hidden, h32 = _bert(P, f"{t}.{3 * i + 1}", hidden, h32, key_bias, True, kv_len, max_kv=max_kv)
-            tok, relu_coef = dyconv_layer(i)
+            tok, relu_coef, v_next = dyconv_layer(i)
             if trace is not None:
                 rec.update(bert_hidden=hidden if h32 is None else h32, dyconv_tok=relu_applied_copy())
                 trace.append(rec)
@@ -929,7 +976,7 @@ def vldyhead(P, cfg, feats, lang, trace=None):
                 if i + 1 < L:
                     prep = vl_text_prep(P, f"{t}.{3 * (i + 1)}.b_attn", hidden, key_bias, h32)
             tok = vl_image_side(P, b, v_ln, cur, kv_len, max_kv)
-            tok, relu_coef = dyconv_layer(i)
+            tok, relu_coef, v_next = dyconv_layer(i)
         main.wait_stream(text)
         keep.clear()
     emb = F.normalize((hidden if h32 is None else h32).float(), p=2, dim=-1)

@@ -50,10 +50,13 @@ _SIGNATURES = {
     "mq_dyconv_fuse": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _l, _vp, _i, _i, _i, _i, _vp]),
     "mq_dyrelu_coef": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mq_dyconv_epilogue_group": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "mq_dyconv_coef_relu_group": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "mq_dyconv_fuse_act_group": (_i, [_vp, _i, _vp, _vp, _f, _i, _i, _i, _vp]),
     "mq_add_upsample_nearest": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "mq_pool2x2_tokens_fwd": (_i, [_vp, _i, _vp, _i, _i, _vp]),
     "mq_dyrelu_ln_fwd": (_i, [_vp, _l, _vp, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
     "mq_dyrelu_apply": (_i, [_vp, _vp, _i, _i, _i, _l, _vp]),
+    "mq_dyrelu_apply_group": (_i, [_vp, _l, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mq_align_scores_fwd": (_i, [_vp, _i, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _l, _i, _vp]),
     "mq_align_fused_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "mq_box_decode": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
@@ -84,7 +87,7 @@ _SIGNATURES = {
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
               "mq_layernorm_fwd", "mq_layernorm2_fwd", "mq_layernorm_clamp_fwd", "mq_clamp_gelu_clamp", "mq_patch_merge_ln_fwd", "mq_swin_mlp2_fwd", "mq_conv3x3_fwd", "mq_conv3x3_nchw32_fwd", "mq_conv3x3_nchw32_v2_fwd", "mq_conv3x3_nchw32_group_fwd", "mq_dcnv2_fwd", "mq_dcnv2_group_fwd",
-              "mq_dyconv_stats", "mq_dyconv_coef", "mq_dyconv_coef_group", "mq_dyconv_fuse", "mq_dyrelu_coef", "mq_dyconv_epilogue_group", "mq_dyrelu_apply", "mq_dyrelu_ln_fwd", "mq_add_upsample_nearest", "mq_pool2x2_tokens_fwd",
+              "mq_dyconv_stats", "mq_dyconv_coef", "mq_dyconv_coef_group", "mq_dyconv_fuse", "mq_dyrelu_coef", "mq_dyconv_epilogue_group", "mq_dyconv_coef_relu_group", "mq_dyconv_fuse_act_group", "mq_dyrelu_apply", "mq_dyrelu_apply_group", "mq_dyrelu_ln_fwd", "mq_add_upsample_nearest", "mq_pool2x2_tokens_fwd",
               "mq_align_scores_fwd", "mq_align_fused_fwd", "mq_box_decode", "mq_roi_align_fwd", "mq_msdeform_attn_fwd", "mq_msdeform_attn_q_fwd")
 # ... and as <name>_f32 (fp32 operands, the precise mode), except ROIAlign: its base entry point already takes fp32 features (is_f32 flag) and has
 # no other 16-bit operand.  (Round 6: the MSDeformAttn kernels have the twin -- the fused-query form reads a 16-bit `qproj`, a float there.)
@@ -1167,6 +1170,62 @@ def dyconv_epilogue_group(levels, w0, b0, w2, b2, relu_coef):
     return relu_coef
 
 
+def dyconv_coef_relu_group(items, attn_w, attn_b, groups, eps, w0, b0, w2, b2, nlevels):
+    """dyconv_coef_group AND the DYReLU coefficients of every level in one launch (mq_dyconv_coef_relu_group): the spatial mean of the fused
+    map follows from the DCN statistics, mean = sum_k (coef_k[..., 0] * s2_k + coef_k[..., 1]).  items: as for dyconv_coef_group plus
+    "level" (0 .. nlevels - 1, <= 3 branches each) -> (list of coef [B,C,2] fp32, bit-equal to dyconv_coef_group's, relu_coef [nlevels,B,4,C] fp32)."""
+    lib = load_library()
+    _need_gpu(attn_w, attn_b, w0, b0, w2, b2)
+    arr = (_CoefBranch * len(items))()
+    lv = (ctypes.c_int * len(items))(*[int(it["level"]) for it in items])
+    outs = []
+    B = C = None
+    for a, it in zip(arr, items):
+        sums = it["sums"]
+        _need_gpu(sums, it["gamma"], it["beta"])
+        assert sums.dtype == torch.float32 and sums.is_contiguous() and sums.shape[2:] == (256, 3) and it["gamma"].dtype == w0.dtype
+        B, C = sums.shape[0], sums.shape[2]
+        coef = torch.empty(B, C, 2, dtype=torch.float32, device=sums.device)
+        a.sums, a.gamma, a.beta, a.coef = _ptr(sums).value, _ptr(it["gamma"]).value, _ptr(it["beta"]).value, _ptr(coef).value
+        a.nblk, a.n, a.nbranches, a.reserved = sums.shape[1], int(it["n"]), int(it["nbranches"]), 0
+        outs.append(coef)
+    assert 0 < nlevels <= 8 and len(items) <= 16 and w0.is_contiguous() and w2.is_contiguous() and w0.dtype in _H16
+    assert all(sum(1 for it in items if it["level"] == l) in (1, 2, 3) for l in range(nlevels)) and all(0 <= it["level"] < nlevels for it in items)
+    relu_coef = torch.empty(nlevels, B, 4, C, dtype=torch.float32, device=w0.device)
+    _chk(_fn(lib, "mq_dyconv_coef_relu_group", w0)(ctypes.cast(arr, _vp), len(items), ctypes.cast(lv, _vp), nlevels, _ptr(attn_w), _ptr(attn_b), _ptr(w0), _ptr(b0),
+                                                   _ptr(w2), _ptr(b2), _ptr(relu_coef), B, C, groups, float(eps), _stream()), "mq_dyconv_coef_relu_group")
+    return outs, relu_coef
+
+
+def dyconv_fuse_act_group(levels, relu_coef, gamma=None, beta=None, eps=1e-5):
+    """The fuse pass of dyconv_epilogue_group with DYReLU (relu_coef [NL,B,4,C] fp32, given) applied per position, then -- gamma / beta given --
+    LayerNorm over the channels: `out` of the levels are slices of the next fusion layer's LN(v); without them the DYReLU result is rounded
+    to 16 bits (fuse + dyrelu_apply_).  mq_dyconv_fuse_act_group; levels: list of (branches, H, W, out) as for dyconv_epilogue_group."""
+    lib = load_library()
+    _need_gpu(relu_coef, gamma, beta)
+    y0 = levels[0][0][0][0]
+    B, _, C = y0.shape
+    assert 0 < len(levels) <= 8 and C == 256 and relu_coef.shape == (len(levels), B, 4, C) and relu_coef.is_contiguous() and relu_coef.dtype == torch.float32
+    assert y0.dtype in _H16 and (gamma is None) == (beta is None)
+    assert gamma is None or (gamma.dtype == beta.dtype == y0.dtype and gamma.is_contiguous() and beta.is_contiguous() and gamma.numel() == beta.numel() == C)
+    arr = (_FuseLevel * len(levels))()
+    nbytes = 0
+    for l, (a, (branches, H, W, out)) in enumerate(zip(arr, levels)):
+        assert out.shape == (B, H * W, C) and out.dtype == y0.dtype and out.stride(2) == 1 and out.stride(1) == C and 1 <= len(branches) <= 3
+        _need_gpu(out)
+        for k, (y, cf, hs, ws) in enumerate(branches):
+            _need_gpu(y, cf)
+            assert y.is_contiguous() and cf.is_contiguous() and y.shape == (B, hs * ws, C) and y.dtype == y0.dtype and cf.dtype == torch.float32
+            a.y[k], a.coef[k], a.hs[k], a.ws[k] = _ptr(y).value, _ptr(cf).value, hs, ws
+            nbytes += y.numel() * 2
+        a.nbranches, a.H, a.W, a.reserved = len(branches), H, W, 0
+        a.out, a.out_bs, a.pool, a.relu_coef = _ptr(out).value, out.stride(0), None, _ptr(relu_coef[l]).value
+        nbytes += B * H * W * C * 2
+    with _timed("dyconv_epilogue_group", nbytes):
+        _chk(_fn(lib, "mq_dyconv_fuse_act_group", y0)(ctypes.cast(arr, _vp), len(levels), _ptr(gamma), _ptr(beta), float(eps), 1 if gamma is not None else 0,
+                                                      B, C, _stream()), "mq_dyconv_fuse_act_group")
+
+
 def dyrelu_(x, pool, w0, b0, w2, b2):
     """In-place DYReLU on x [B,n,C] fp16 (contiguous rows, any batch stride) given pool [B,C] = sum over positions of x."""
     lib = load_library()
@@ -1249,6 +1308,24 @@ def dyrelu_apply_(x, coef):
     B, n, C = x.shape
     assert x.stride(2) == 1 and x.stride(1) == C and x.dtype in _H16 and coef.shape == (B, 4, C) and coef.is_contiguous()
     _chk(_fn(lib, "mq_dyrelu_apply", x)(_ptr(x), _ptr(coef), B, n, C, x.stride(0), _stream()), "mq_dyrelu_apply")
+    return x
+
+
+def dyrelu_apply_group_(x, coef, sizes):
+    """In-place DYReLU on the whole pyramid token buffer x [B,N,C] 16-bit (rows contiguous, any batch stride) in one launch
+    (mq_dyrelu_apply_group): coef [NL,B,4,C] fp32, sizes = [(H, W)] of the NL <= 8 levels concatenated along N.  The bits of dyrelu_apply_
+    level by level."""
+    lib = load_library()
+    _need_gpu(x, coef)
+    B, N, C = x.shape
+    NL = len(sizes)
+    offs = [0]
+    for (h, w) in sizes:
+        offs.append(offs[-1] + int(h) * int(w))
+    assert 0 < NL <= 8 and C % 8 == 0 and offs[-1] == N and x.stride(2) == 1 and x.stride(1) == C and x.dtype in _H16
+    assert coef.shape == (NL, B, 4, C) and coef.is_contiguous() and coef.dtype == torch.float32
+    rf = (ctypes.c_int * (NL + 1))(*offs)
+    _chk(_fn(lib, "mq_dyrelu_apply_group", x)(_ptr(x), x.stride(0), _ptr(coef), ctypes.cast(rf, _vp), NL, B, N, C, _stream()), "mq_dyrelu_apply_group")
     return x
 
 

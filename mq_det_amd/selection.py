@@ -34,6 +34,21 @@ KERNEL_DEFAULTS = {
     "DYCONV_EPILOGUE_GROUPED": 1,  # 1: mq_dyconv_epilogue_group -- the fuse pass and the DYReLU coefficients of ALL levels of a DyConv layer in two launches
                                  # on the main stream (were 10 launches on five streams behind a fork / join); equal results.  A/B of round 5
                                  # (GPU call 1, 3 alternations x 60 steps): 439.2 / 440.8 / 437.8 against 433.7 / 439.1 / 435.0 images/s: +0.8 %, default
+    "DYCONV_EPILOGUE_LN": 0,     # 1: the DYReLU coefficients from the DCN statistics (mq_dyconv_coef_relu_group: mean(out) = sum_k A_k s2_k + B_k, no pass over
+                                 # the fused map) and the fuse pass applies DYReLU and the NEXT layer's layer_norm_v itself (mq_dyconv_fuse_act_group): per
+                                 # fusion layer mq_dyrelu_ln_fwd and the DYReLU-coefficient launch go, after the last layer the five mq_dyrelu_apply behind
+                                 # their fork / join.  Needs DYRELU_IN_LN = 1 and DYCONV_EPILOGUE_GROUPED = 1; 0 (or either of those 0): the path above,
+                                 # unchanged.  Same arithmetic downstream of the DYReLU coefficients; those are the fp32 mean of the unrounded map instead
+                                 # of the sum of the 16-bit outputs.  Same-box A/B, 3 alternations x 30 steps:
+                                 # 527.9 / 527.1 / 529.1 against 501.7 / 491.5 / 505.7 images/s (parent on that box: 500.5): +5.7 %, 16.01 -> 15.15 ms per step
+                                 # (profiles/dyconv_epilogue_ln_ab.txt).  OFF by default all the same: with other DYReLU coefficients the benchmark's
+                                 # detections are not the parent's (scores move by up to 4e-2, near-ties at the 300th score reorder: no array of
+                                 # --dump-outputs is equal), and most of the gain is the fork / join, which DYRELU_APPLY_GROUPED removes with equal bits
+    "DYRELU_APPLY_GROUPED": 1,   # 1: mq_dyrelu_apply_group -- the DYReLU of the LAST DyConv layer on all levels of the token buffer in one launch on the
+                                 # main stream (were five mq_dyrelu_apply on five streams behind a fork / join of the captured graph); bit-equal
+                                 # outputs (--dump-outputs equal to the parent's array for array).  Same-box A/B, 3 alternations x 30 steps:
+                                 # 509.5 / 510.3 / 512.0 against 497.1 / 495.0 / 492.8 images/s (parent on that box: 496.3): +3.1 %, 16.16 -> 15.67 ms
+                                 # per step (profiles/dyconv_epilogue_ln_ab.txt, section 6)
     "BERT_CLAMP_FUSED": 1,       # (round 5, GPU call 1: 0.6 % slower, three of three, and call 11 of round 6 again: off until the end of round 6.  On the final
                                  # step -- GPU call 28 -- a tie: 503.0 against 502.8 images/s over three alternations; on since: 36 torch launches per step
                                  # fewer, the torch-native share of an eager step 9.4 -> see profiles/r06_call29_per_step_summary.txt)
