@@ -578,6 +578,16 @@ int mq_flickr_tally(const int* hits, const int* cat_off, const int* cat_idx, uns
  * (strict; NaN compares false).  Admitted rows are copied bit for bit.  Every label label_lo .. label_lo + num_labels - 1 must be < labels. */
 int mq_bank_admit(const float* cand, const long long* sorted_labels, const long long* order, float* pool, float* inv_norm, int* slots, int* counts,
                   int* state, int N, int D, int pool_rows, int cap, int label_lo, int num_labels, int maxq, int exclude, float thr, void* stream);
+/* The vision queries of a forward, selected from the bank in one launch (query_selector.py:60-116 without the per-label copies, torch.cat and
+ * pad_sequence).  pool [pool_rows, S, C] fp32 and slots [num_labels, cap] int32 as above; qsrc [I, Q, 2] int32 = per item and selected query
+ * (label, position in the label's slot row), -1 = padding; qtok [I, Q, MT] int32 = the token positions of that query's label, -1 padded.
+ * -> vision [I, Q * S, C] (out_type 0: fp32, 1: fp16, 2: bf16): row q * S + s = pool[slots[label, pos], s, :] rounded to nearest-even, zeros for
+ *    padding (and for an entry that names no row of the tables: nothing is read out of bounds);
+ * -> idx [I, T, Smax] int32: for token t the vision rows of every query whose label lists t, ascending, -1 padded; a token a label lists twice
+ *    gives each of its rows twice, adjacent.  Smax >= the longest such list (the host knows it; longer lists are cut).
+ * S in 1 .. 8; any C (16-byte path when C % 4 == 0 and the buffers are 16-byte aligned).  No host synchronisation, no allocation. */
+int mq_bank_select_fwd(const float* pool, const int* slots, const int* qsrc, const int* qtok, void* vision, int* idx, int pool_rows, int num_labels,
+                       int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int out_type, void* stream);
 
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --

@@ -1,4 +1,5 @@
-// The vision-query bank's admission loop on the device (host side: mq_det_amd/query_bank.py QueryBank.update).
+// The vision-query bank on the device: its admission loop (host side: mq_det_amd/query_bank.py QueryBank.update) and, at the end of the file,
+// the selection of a forward's vision queries from it (mq_bank_select_fwd).
 //
 // mq_bank_admit: generalized_vl_rcnn_new.py:269-287 (== groundingdino.py:401-421) for a whole batch of candidates in one launch.  The host
 // sorts the candidates' labels once (stable: candidates of a label keep their row order); workgroup b owns label `label_lo + b`, finds its
@@ -130,6 +131,127 @@ extern "C" int mq_bank_admit(const float* cand, const long long* sorted_labels, 
     hipLaunchKernelGGL(bank_admit_kernel<false>, dim3(num_labels), dim3(BANK_THREADS), 0, (hipStream_t)stream, cand, sorted_labels, order, pool,
                        inv_norm, slots, counts, state, N, D, pool_rows, cap, label_lo, maxq, exclude, thr);
   return (int)hipGetLastError();
+}
+
+// mq_bank_select_fwd: the consumer side (host: modeling/query_selector.py QuerySelector with a resident QueryBank).  The host has drawn, per
+// item and label, which of the label's rows enter the forward; one launch turns those integer tables into what the GCP layers read:
+//   * row tiles (blockIdx.x < row_tiles): SEL_ROWS consecutive rows of vision [I * V, C], one wave per row at a time.  Row (i, q * S + s) is
+//     pool row slots[label, pos] of qsrc[i, q], scale s, read with 16-byte loads (1 KB per wave instruction at C = 256) and stored in the
+//     output type, rounded to nearest-even like Tensor.to; a padding query, or one whose table entries do not name a row, gives zeros.
+//   * index blocks (the rest of the grid): 256 token positions of one item each.  The item's qtok [Q, MT] goes through LDS in pieces of
+//     SEL_CHUNK entries; every thread walks the queries in order and counts how often its token is listed, so its rows come out ascending
+//     and a token listed twice gives each row twice, adjacent -- `sorted(owners[t])` of the dict path.  Smax is the host's exact maximum.
+// Nothing here waits for another workgroup; the two parts write disjoint outputs.
+#define SEL_THREADS 256
+#define SEL_ROWS 16
+#define SEL_CHUNK 2048
+
+struct sel_bf16 { unsigned short bits; };
+template <class O> struct alignas(4 * sizeof(O)) sel_vec4 { O v[4]; };
+
+__device__ __forceinline__ void sel_cvt(float x, float& y) { y = x; }
+__device__ __forceinline__ void sel_cvt(float x, _Float16& y) { y = (_Float16)x; }
+__device__ __forceinline__ void sel_cvt(float x, sel_bf16& y) {            // c10::BFloat16's round-to-nearest-even
+  const unsigned u = __builtin_bit_cast(unsigned, x);
+  y.bits = x != x ? (unsigned short)0x7FC0 : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <class O, bool VEC4>
+__global__ __launch_bounds__(SEL_THREADS) void bank_select_kernel(const float* __restrict__ pool, const int* __restrict__ slots,
+                                                                   const int* __restrict__ qsrc, const int* __restrict__ qtok,
+                                                                   O* __restrict__ vision, int* __restrict__ idx, int pool_rows, int num_labels,
+                                                                   int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int row_tiles) {
+  __shared__ int tok_s[SEL_CHUNK];
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x < row_tiles) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const long rows = (long)I * Q * S;
+    for (int r = wave; r < SEL_ROWS; r += SEL_THREADS / 64) {
+      const long row = (long)blockIdx.x * SEL_ROWS + r;      // = (i * Q + q) * S + s
+      if (row >= rows) break;
+      const long iq = row / S;
+      const int s = (int)(row - iq * S);
+      const int label = qsrc[iq * 2], pos = qsrc[iq * 2 + 1];
+      const float* __restrict__ src = nullptr;
+      if (label >= 0 && label < num_labels && pos >= 0 && pos < cap) {
+        const int prow = slots[(long)label * cap + pos];
+        if (prow >= 0 && prow < pool_rows) src = pool + ((long)prow * S + s) * C;
+      }
+      O* __restrict__ dst = vision + row * C;
+      if (VEC4) {
+        for (int k = lane * 4; k < C; k += 256) {
+          float4_ x = {0.f, 0.f, 0.f, 0.f};
+          if (src) x = *(const float4_*)(src + k);
+          sel_vec4<O> y;
+          sel_cvt(x[0], y.v[0]);
+          sel_cvt(x[1], y.v[1]);
+          sel_cvt(x[2], y.v[2]);
+          sel_cvt(x[3], y.v[3]);
+          *(sel_vec4<O>*)(dst + k) = y;
+        }
+      } else {
+        for (int k = lane; k < C; k += 64) sel_cvt(src ? src[k] : 0.f, dst[k]);
+      }
+    }
+    return;
+  }
+  const int tblocks = (T + SEL_THREADS - 1) / SEL_THREADS;
+  const int b = blockIdx.x - row_tiles, i = b / tblocks, t = (b - i * tblocks) * SEL_THREADS + tid;
+  const int* __restrict__ tok = qtok + (long)i * Q * MT;
+  int* __restrict__ out = idx + ((long)i * T + (t < T ? t : 0)) * Smax;      // written with t < T only
+  const int total = Q * MT;
+  int n = 0, q = 0, j = 0, mult = 0;
+  for (int base = 0; base < total; base += SEL_CHUNK) {
+    const int len = total - base < SEL_CHUNK ? total - base : SEL_CHUNK;
+    __syncthreads();                                         // the previous piece has been read by every thread
+    for (int e = tid; e < len; e += SEL_THREADS) tok_s[e] = tok[base + e];
+    __syncthreads();
+    if (t < T) {
+      for (int e = 0; e < len; ++e) {
+        mult += tok_s[e] == t;
+        if (++j == MT) {                                     // query q is complete: its S rows, each `mult` times
+          if (mult) {
+            for (int s = 0; s < S; ++s)
+              for (int m = 0; m < mult; ++m)
+                if (n < Smax) out[n++] = q * S + s;
+          }
+          j = 0;
+          mult = 0;
+          ++q;
+        }
+      }
+    }
+  }
+  if (t < T)
+    for (; n < Smax; ++n) out[n] = -1;
+}
+
+template <class O>
+static int bank_select_launch(const float* pool, const int* slots, const int* qsrc, const int* qtok, void* vision, int* idx, int pool_rows,
+                              int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax, hipStream_t stream) {
+  const long rows = (long)I * Q * S;
+  const long row_tiles = (rows + SEL_ROWS - 1) / SEL_ROWS, blocks = row_tiles + (long)I * ((T + SEL_THREADS - 1) / SEL_THREADS);
+  if (blocks > 0x7fffffffL) return -1;
+  const bool vec4 = C % 4 == 0 && ((uintptr_t)pool | (uintptr_t)vision) % 16 == 0;
+  if (vec4)
+    return mq_launch<bank_select_kernel<O, true>>(dim3((unsigned)blocks), dim3(SEL_THREADS), 0, stream, pool, slots, qsrc, qtok, (O*)vision, idx,
+                                                  pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, (int)row_tiles);
+  return mq_launch<bank_select_kernel<O, false>>(dim3((unsigned)blocks), dim3(SEL_THREADS), 0, stream, pool, slots, qsrc, qtok, (O*)vision, idx,
+                                                 pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, (int)row_tiles);
+}
+
+extern "C" int mq_bank_select_fwd(const float* pool, const int* slots, const int* qsrc, const int* qtok, void* vision, int* idx, int pool_rows,
+                                  int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int out_type, void* stream) {
+  if (I <= 0) return 0;
+  if (Q <= 0 || MT <= 0 || S < 1 || S > 8 || C <= 0 || T <= 0 || Smax <= 0 || pool_rows < 0 || num_labels < 0 || cap < 0) return -1;
+  if ((long)Q * MT > 0x7fffffffL) return -1;
+  const hipStream_t st = (hipStream_t)stream;
+  switch (out_type) {
+    case 0: return bank_select_launch<float>(pool, slots, qsrc, qtok, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, st);
+    case 1: return bank_select_launch<_Float16>(pool, slots, qsrc, qtok, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, st);
+    case 2: return bank_select_launch<sel_bf16>(pool, slots, qsrc, qtok, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, st);
+  }
+  return -1;
 }
 
 #endif

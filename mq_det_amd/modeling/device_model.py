@@ -120,6 +120,7 @@ class DeviceModel(GraphRunner, nn.Module):
         return super().train(False)
 
     def load_query_bank(self, query_path):
+        """A bank file's path, the `{label: Tensor[n, scales, C]}` dict, or a device-resident `QueryBank` (selected from on the device)."""
         self.query_selector.load_query_bank(query_path)
 
     def _use_vq(self):

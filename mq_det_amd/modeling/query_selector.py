@@ -6,6 +6,8 @@ MI355X-first difference: besides the dense mask the selector emits the gather in
 vision rows each text token may attend to) that the reference re-derives from the mask with a top-k trick in
 EACH of the 6 GCP layers (modeling_bert_new.py:40-63,162-184); it is built once, on the host, from the
 positive_map the caller already holds -- no device work, no sync.
+With a device-resident `QueryBank` (mq_det_amd.query_bank) instead of the dict, the draws stay on the host and the rows and the index come
+from one kernel launch (`_select_resident`, csrc/query_bank.hip mq_bank_select_fwd).
 """
 import os
 import random
@@ -13,6 +15,9 @@ import random
 import numpy as np
 import torch
 from torch import nn
+
+from .. import ops as _ops
+from ..query_bank import QueryBank
 
 
 def labels_and_maps(positive_map, T, device="cpu", dtype=torch.float32):
@@ -136,6 +141,7 @@ class QuerySelector(nn.Module):
         # reference run's as soon as one caption did not need a real draw.
         self.reference_rng = bool(cfg.VISION_QUERY.get("REFERENCE_RNG_STREAM", False))
         self.query_bank = None
+        self._snapshot = None                                  # host counts of a resident QueryBank at load time (None: dict bank)
         self._dev_bank = {}
         self._sel_cache = {}
         path = cfg.VISION_QUERY.QUERY_BANK_PATH
@@ -145,10 +151,32 @@ class QuerySelector(nn.Module):
             self.load_query_bank(path)
 
     def load_query_bank(self, bank):
-        """`bank`: path to a torch-saved dict or the dict itself: {label: Tensor[n, scales, C]}."""
-        self.query_bank = torch.load(bank, map_location="cpu") if isinstance(bank, (str, os.PathLike)) else bank
+        """`bank`: path to a torch-saved dict or the dict itself: {label: Tensor[n, scales, C]}, or a device-resident `QueryBank`.
+        A `QueryBank` is kept as it is, with a host SNAPSHOT of its counts: its pool and slot table are append-only, so the rows the
+        snapshot names stay where they are whatever is admitted later (also across a reallocation: the bank's current tensors are read at
+        every call), and rows admitted after this call stay invisible until the bank is loaded again."""
+        if isinstance(bank, QueryBank):
+            self.query_bank, self._snapshot = bank, (bank, list(bank._counts()))
+        else:
+            self.query_bank = torch.load(bank, map_location="cpu") if isinstance(bank, (str, os.PathLike)) else bank
+            self._snapshot = None
         self._dev_bank = {}
         self._sel_cache = {}
+
+    def _resident(self):
+        """The counts snapshot of a resident `QueryBank`; None with a dict bank or none.  (A `QueryBank` assigned to `query_bank` without
+        `load_query_bank` is snapshotted at its first use.)"""
+        bank = self.query_bank
+        if not isinstance(bank, QueryBank):
+            return None
+        if self._snapshot is None or self._snapshot[0] is not bank:
+            self._snapshot = (bank, list(bank._counts()))
+        return self._snapshot[1]
+
+    def _count(self, label):
+        """Rows of a label in the resident bank's snapshot (0: none, not an integer label, or beyond the table)."""
+        snap = self._resident()
+        return snap[label] if isinstance(label, (int, np.integer)) and 0 <= label < len(snap) else 0
 
     def _candidates(self, label):
         """Bank entry of a label; None when the label has no vision query.  Reference banks are `defaultdict(list)`
@@ -162,6 +190,8 @@ class QuerySelector(nn.Module):
 
     def has_vision_query(self, label):
         """The reference's `has_vision_query` flag of a label (query_selector.py:77-78): the bank holds at least one row for it."""
+        if self._resident() is not None:
+            return self._count(label) > 0
         return self._candidates(label) is not None
 
     def deterministic(self, labels):
@@ -171,6 +201,8 @@ class QuerySelector(nn.Module):
         (With VISION_QUERY.REFERENCE_RNG_STREAM nothing is memoised: every label of every forward consumes its draw.)"""
         if self.reference_rng:
             return False
+        if self._resident() is not None:
+            return all(self._count(lab) <= self.num_query_per_class for lab in labels)
         for lab in labels:
             cand = self._candidates(lab)
             if cand is not None and len(cand) > self.num_query_per_class:
@@ -182,6 +214,13 @@ class QuerySelector(nn.Module):
         draw: consume numpy's global generator exactly like the reference does for EVERY label (:74), also when the draw is
         the identity -- used when some label of the caption holds more than k rows, so that the same seed gives the same
         selection as the reference."""
+        if self._resident() is not None:                            # resident bank (only `forward`, the reference-shaped output, comes here)
+            pos = self._draw(self._count(label), draw)
+            if len(pos) == 0:
+                return None
+            bank = self.query_bank
+            rows = bank.slots[label].index_select(0, torch.from_numpy(pos).to(bank.slots.device)).long()
+            return bank.pool[rows].flatten(0, 1).to(device=device, dtype=dtype)
         cand = self._candidates(label)
         k = self.num_query_per_class
         if draw:
@@ -198,7 +237,17 @@ class QuerySelector(nn.Module):
             self._dev_bank[key] = cand[:k].flatten(0, 1).to(device=device, dtype=dtype)
         return self._dev_bank[key]
 
+    def _draw(self, n_tot, draw):
+        """Positions in a label's slot row that enter a forward, ascending (int64 array): the reference's draw (:74) when `draw`, consumed
+        also when the label has no rows or the draw is the identity; else the first min(n, k)."""
+        k = self.num_query_per_class
+        if draw:
+            return np.sort(np.random.choice(n_tot, min(n_tot, k), replace=False)).astype(np.int64)
+        return np.arange(min(n_tot, k), dtype=np.int64)
+
     def _width(self):
+        if self._resident() is not None:
+            return 1 if self.query_bank.pool is None else self.query_bank.pool.shape[-1]
         for v in self.query_bank.values():
             if torch.is_tensor(v) and v.numel():
                 return v.shape[-1]
@@ -207,6 +256,8 @@ class QuerySelector(nn.Module):
     def select(self, batched_labels, batched_positive_maps, T, device, dtype):
         """-> vision [B, V, C] (zero padded), idx [B, T, S] int32 (-1 padded).  Labels without bank rows are skipped
         (text-only for that label, like the reference)."""
+        if self._resident() is not None:
+            return self._select_resident(batched_labels, batched_positive_maps, T, device, dtype)
         per_image, tok_lists = [], []
         for labels, pmap in zip(batched_labels, batched_positive_maps):
             rows, owners = [], [[] for _ in range(T)]
@@ -230,6 +281,67 @@ class QuerySelector(nn.Module):
                 if o:
                     idx[b, t, :len(o)] = torch.tensor(sorted(o), dtype=torch.int32)
         return vision.contiguous(), idx.to(device, non_blocking=True)
+
+    def _select_resident(self, batched_labels, batched_positive_maps, T, device, dtype):
+        """`select` from a resident `QueryBank`: the draws of the dict path in its order (numpy's global generator ends in the same state),
+        two integer tables built with numpy -- qsrc [I, Q, 2] = (label, position in the label's slot row) and qtok [I, Q, MT] = the label's
+        token positions per selected query, -1 padded --, ONE upload and ONE launch (ops.bank_select) that writes the padded vision rows in
+        `dtype` and the gather index.  No per-label copies, no torch.cat / pad_sequence, no loop over the T token positions."""
+        bank, I = self.query_bank, len(batched_labels)
+        e_item, e_lab, e_tok, e_pos = [], [], [], []              # one entry per (item, label with rows)
+        toks, tok_of = [], {}                                     # distinct token lists of this call: (id(map), label) -> row of tokU
+        snap, k = self._resident(), self.num_query_per_class
+        first = [np.arange(n, dtype=np.int64) for n in range(k + 1)]          # the identity selections (read only)
+        for i, (labels, pmap) in enumerate(zip(batched_labels, batched_positive_maps)):
+            ns = [snap[lab] if isinstance(lab, (int, np.integer)) and 0 <= lab < len(snap) else 0 for lab in labels]
+            draw = self.reference_rng or max(ns, default=0) > k                # not self.deterministic(labels)
+            for lab, n in zip(labels, ns):
+                if draw:                                                       # (also for a label without rows: the draw is consumed)
+                    pos = self._draw(n, True)
+                if n == 0:
+                    continue
+                if not draw:
+                    pos = first[min(n, k)]
+                u = tok_of.get((id(pmap), lab))
+                if u is None:
+                    t = np.asarray(pmap[lab], dtype=np.int64).reshape(-1)
+                    if len(t) and (t.min() < -T or t.max() >= T):
+                        raise IndexError(f"label {lab}: token position out of range for {T} positions")
+                    u = tok_of[(id(pmap), lab)] = len(toks)
+                    toks.append(np.where(t < 0, t + T, t))
+                e_item.append(i)
+                e_lab.append(lab)
+                e_tok.append(u)
+                e_pos.append(pos)
+        if not e_pos:                                             # what pad_sequence makes of I empty images: callers fall back to text only
+            return (torch.zeros(I, 0, self._width(), device=device, dtype=dtype),
+                    torch.full((I, T, 1), -1, dtype=torch.int32).to(device, non_blocking=True))
+        S = bank.pool.shape[1]
+        e_item, e_lab, e_tok = np.asarray(e_item), np.asarray(e_lab), np.asarray(e_tok)
+        e_n = np.asarray([len(p) for p in e_pos])
+        per_item = np.bincount(e_item, weights=e_n, minlength=I).astype(np.int64)
+        Q, MT = int(per_item.max()), max(1, max(len(t) for t in toks))
+        tokU = np.full((len(toks), MT), -1, dtype=np.int32)
+        for u, t in enumerate(toks):
+            tokU[u, :len(t)] = t
+        # every selected query: its entry, its item and its place q inside the item (entries are in item order already)
+        q_e = np.repeat(np.arange(len(e_n)), e_n)
+        q_item = e_item[q_e]
+        q_in = np.arange(len(q_e)) - (np.cumsum(per_item) - per_item)[q_item]
+        tab = np.full(I * Q * (2 + MT), -1, dtype=np.int32)       # qsrc and qtok in one buffer: one upload
+        qsrc, qtok = tab[:I * Q * 2].reshape(I, Q, 2), tab[I * Q * 2:].reshape(I, Q, MT)
+        qsrc[q_item, q_in, 0] = e_lab[q_e]
+        qsrc[q_item, q_in, 1] = np.concatenate(e_pos)
+        qtok[q_item, q_in] = tokU[e_tok[q_e]]
+        # the longest owner list: rows per (item, token) = sum over the entries that list the token of n * S, counted with multiplicity
+        tokE = tokU[e_tok]
+        live = tokE >= 0
+        owners = np.zeros(I * T, dtype=np.int64)
+        np.add.at(owners, (e_item[:, None] * T + tokE)[live], np.broadcast_to((e_n * S)[:, None], tokE.shape)[live])
+        smax = max(1, int(owners.max()))
+        dev_tab = torch.from_numpy(tab).to(bank.pool.device, non_blocking=True)
+        vision, idx = _ops.bank_select(bank.pool, bank.slots, dev_tab[:I * Q * 2].view(I, Q, 2), dev_tab[I * Q * 2:].view(I, Q, MT), T, smax, dtype)
+        return vision.to(device), idx.to(device)
 
     def select_cached(self, key, labels, positive_map, B, T, device, dtype):
         """Memoised `select` for B images sharing one caption (eval protocol): no per-call host or device work."""

@@ -6,6 +6,8 @@ admission order, counts [labels] and the cached 1 / max(|row|, 1e-12) of every r
 batch of candidates in ONE kernel launch (csrc/query_bank.hip mq_bank_admit) with the reference's sequential semantics; `to_dict` / `save`
 give back exactly what the dict path would hold.  `pool_into_bank` (modeling/detector.py) takes this path when `extract_query` is handed a
 `QueryBank` as `query_images`, for MQ-GLIP and MQ-GroundingDINO alike; a dict takes the Python loop it always took.
+`model.load_query_bank(bank)` hands the bank to the forward as it is: the selector (modeling/query_selector.py) snapshots its counts and selects
+the vision queries of every call from `pool` / `slots` with one launch (mq_bank_select_fwd).
 
 `extract_query_bank` is the extraction loop of tools/train_net.py:294-336 and `online_update` the test-time refinement of
 engine/inference.py:383-499 (called from tools/test_grounding_net.py:181-227)."""
@@ -227,7 +229,7 @@ def extract_query_bank(model, batches, max_query_number=None, save_path=None):
 
 
 @torch.no_grad()
-def online_update(model, data_loader, device="cuda", cfg=None, num_turns=1, save_name=None, *, queries_and_maps):
+def online_update(model, data_loader, device="cuda", cfg=None, num_turns=1, save_name=None, *, queries_and_maps, resident=False):
     """Test-time refinement of the bank (engine/inference.py:383-499): per turn, every batch of `data_loader` is detected with every chunk
     caption, the detections of an image are concatenated in chunk order, those with score > VISION_QUERY.SCORE_THRESHOLD (strict) are
     pooled from the backbone features and admitted with `exclude_similar=True` up to VISION_QUERY.MAX_TEST_QUERY_NUMBER per label; the
@@ -238,6 +240,9 @@ def online_update(model, data_loader, device="cuda", cfg=None, num_turns=1, save
     reference.  The bank starts from VISION_QUERY.QUERY_BANK_PATH when that file exists, else empty.
     The detections come from `model(...)`: with VISION_QUERY.MASK_DURING_INFERENCE (vision-only evaluation, detector._masked_ids) the words of
     the labels the model's bank has rows for are masked, and `model.load_query_bank` between turns changes that set with the bank.
+    `resident=True`: the model is handed the `QueryBank` itself between turns and after the last one (`QuerySelector.load_query_bank` keeps
+    it with a snapshot of its counts and selects from it on the device) instead of reading the file back as a CPU dict; the file is written
+    every turn all the same, and the rows admitted during a turn still enter the forward only at the next load.
 
     Two deliberate differences from the reference:
       * batches of more than one image are accepted (the reference asserts 1, "TODO: support batched outputs").  The bank only enters the
@@ -259,7 +264,7 @@ def online_update(model, data_loader, device="cuda", cfg=None, num_turns=1, save
     subset = cfg.TEST.get("SUBSET", -1)
     for turn in range(num_turns):
         if turn > 0:
-            model.load_query_bank(save_name)
+            model.load_query_bank(bank if resident else save_name)
         model.eval()
         for i, batch in enumerate(data_loader):
             if i == subset:
@@ -278,4 +283,6 @@ def online_update(model, data_loader, device="cuda", cfg=None, num_turns=1, save
                 bank = model.extract_query(targets=kept, query_images=bank, visual_features=feats, exclude_similar=True, device=device,
                                            max_query_number=VQ.MAX_TEST_QUERY_NUMBER)
         bank.save(save_name)
+    if resident:
+        model.load_query_bank(bank)
     return model
