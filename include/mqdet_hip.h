@@ -588,6 +588,14 @@ int mq_bank_admit(const float* cand, const long long* sorted_labels, const long 
  * S in 1 .. 8; any C (16-byte path when C % 4 == 0 and the buffers are 16-byte aligned).  No host synchronisation, no allocation. */
 int mq_bank_select_fwd(const float* pool, const int* slots, const int* qsrc, const int* qtok, void* vision, int* idx, int pool_rows, int num_labels,
                        int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int out_type, void* stream);
+/* The same launch with a per-position addend (VISION_QUERY.ADD_VISION_LAYER, query_selector.py:98-99): row_add [add_rows, C] fp32 =
+ * `tunable_vision_linear.weight`.  Row v = q * S + s of an item that names a row of the tables is round(fp32(pool row) + row_add[v, :]) -- one
+ * fp32 sum, one rounding to out_type; a padding row stays zero (the reference adds before pad_sequence).  row_add is read only for such rows and
+ * never at or beyond add_rows: the host refuses an item with more than add_rows real rows before the launch.  The 16-byte path also needs
+ * row_add 16-byte aligned.  Same kernel body, same tail of arguments, same idx. */
+int mq_bank_select_add_fwd(const float* pool, const int* slots, const int* qsrc, const int* qtok, const float* row_add, int add_rows, void* vision,
+                           int* idx, int pool_rows, int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int out_type,
+                           void* stream);
 
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --

@@ -156,9 +156,14 @@ __device__ __forceinline__ void sel_cvt(float x, sel_bf16& y) {            // c1
   y.bits = x != x ? (unsigned short)0x7FC0 : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
-template <class O, bool VEC4>
+// ADD (mq_bank_select_add_fwd, VISION_QUERY.ADD_VISION_LAYER): row v = q * S + s of an item, counted inside the item, gets row_add[v, :] added in
+// fp32 before the one rounding to O.  Only a row that the tables name gets it -- a padding row stays zero, as the reference adds before
+// pad_sequence -- and no addend row at or beyond add_rows is read (the host refuses such a call; here the row then goes without).  Without ADD
+// the two arguments are not looked at and the code is that of mq_bank_select_fwd.
+template <class O, bool VEC4, bool ADD>
 __global__ __launch_bounds__(SEL_THREADS) void bank_select_kernel(const float* __restrict__ pool, const int* __restrict__ slots,
                                                                    const int* __restrict__ qsrc, const int* __restrict__ qtok,
+                                                                   const float* __restrict__ row_add, int add_rows,
                                                                    O* __restrict__ vision, int* __restrict__ idx, int pool_rows, int num_labels,
                                                                    int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int row_tiles) {
   __shared__ int tok_s[SEL_CHUNK];
@@ -178,10 +183,22 @@ __global__ __launch_bounds__(SEL_THREADS) void bank_select_kernel(const float* _
         if (prow >= 0 && prow < pool_rows) src = pool + ((long)prow * S + s) * C;
       }
       O* __restrict__ dst = vision + row * C;
+      const float* __restrict__ add = nullptr;                 // decided once per row, outside the element loops
+      if (ADD && src) {
+        const long v = row - (iq / Q) * (long)Q * S;           // the row's place in its item
+        if (v < add_rows) add = row_add + v * C;
+      }
       if (VEC4) {
         for (int k = lane * 4; k < C; k += 256) {
           float4_ x = {0.f, 0.f, 0.f, 0.f};
           if (src) x = *(const float4_*)(src + k);
+          if (ADD && add) {
+            const float4_ a = *(const float4_*)(add + k);
+            x[0] += a[0];
+            x[1] += a[1];
+            x[2] += a[2];
+            x[3] += a[3];
+          }
           sel_vec4<O> y;
           sel_cvt(x[0], y.v[0]);
           sel_cvt(x[1], y.v[1]);
@@ -190,7 +207,11 @@ __global__ __launch_bounds__(SEL_THREADS) void bank_select_kernel(const float* _
           *(sel_vec4<O>*)(dst + k) = y;
         }
       } else {
-        for (int k = lane; k < C; k += 64) sel_cvt(src ? src[k] : 0.f, dst[k]);
+        if (ADD && add) {
+          for (int k = lane; k < C; k += 64) sel_cvt(src[k] + add[k], dst[k]);
+        } else {
+          for (int k = lane; k < C; k += 64) sel_cvt(src ? src[k] : 0.f, dst[k]);
+        }
       }
     }
     return;
@@ -226,32 +247,57 @@ __global__ __launch_bounds__(SEL_THREADS) void bank_select_kernel(const float* _
     for (; n < Smax; ++n) out[n] = -1;
 }
 
-template <class O>
-static int bank_select_launch(const float* pool, const int* slots, const int* qsrc, const int* qtok, void* vision, int* idx, int pool_rows,
-                              int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax, hipStream_t stream) {
+template <class O, bool ADD>
+static int bank_select_launch(const float* pool, const int* slots, const int* qsrc, const int* qtok, const float* row_add, int add_rows,
+                              void* vision, int* idx, int pool_rows, int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax,
+                              hipStream_t stream) {
   const long rows = (long)I * Q * S;
   const long row_tiles = (rows + SEL_ROWS - 1) / SEL_ROWS, blocks = row_tiles + (long)I * ((T + SEL_THREADS - 1) / SEL_THREADS);
   if (blocks > 0x7fffffffL) return -1;
-  const bool vec4 = C % 4 == 0 && ((uintptr_t)pool | (uintptr_t)vision) % 16 == 0;
+  const bool vec4 = C % 4 == 0 && ((uintptr_t)pool | (uintptr_t)vision | (ADD ? (uintptr_t)row_add : 0)) % 16 == 0;
   if (vec4)
-    return mq_launch<bank_select_kernel<O, true>>(dim3((unsigned)blocks), dim3(SEL_THREADS), 0, stream, pool, slots, qsrc, qtok, (O*)vision, idx,
-                                                  pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, (int)row_tiles);
-  return mq_launch<bank_select_kernel<O, false>>(dim3((unsigned)blocks), dim3(SEL_THREADS), 0, stream, pool, slots, qsrc, qtok, (O*)vision, idx,
-                                                 pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, (int)row_tiles);
+    return mq_launch<bank_select_kernel<O, true, ADD>>(dim3((unsigned)blocks), dim3(SEL_THREADS), 0, stream, pool, slots, qsrc, qtok, row_add,
+                                                       add_rows, (O*)vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax,
+                                                       (int)row_tiles);
+  return mq_launch<bank_select_kernel<O, false, ADD>>(dim3((unsigned)blocks), dim3(SEL_THREADS), 0, stream, pool, slots, qsrc, qtok, row_add,
+                                                      add_rows, (O*)vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax,
+                                                      (int)row_tiles);
+}
+
+template <bool ADD>
+static int bank_select_any(const float* pool, const int* slots, const int* qsrc, const int* qtok, const float* row_add, int add_rows, void* vision,
+                           int* idx, int pool_rows, int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int out_type,
+                           void* stream) {
+  if (I <= 0) return 0;
+  if (Q <= 0 || MT <= 0 || S < 1 || S > 8 || C <= 0 || T <= 0 || Smax <= 0 || pool_rows < 0 || num_labels < 0 || cap < 0) return -1;
+  if ((long)Q * MT > 0x7fffffffL) return -1;
+  if (ADD && (!row_add || add_rows < 0)) return -1;
+  const hipStream_t st = (hipStream_t)stream;
+  switch (out_type) {
+    case 0:
+      return bank_select_launch<float, ADD>(pool, slots, qsrc, qtok, row_add, add_rows, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T,
+                                            Smax, st);
+    case 1:
+      return bank_select_launch<_Float16, ADD>(pool, slots, qsrc, qtok, row_add, add_rows, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C,
+                                               T, Smax, st);
+    case 2:
+      return bank_select_launch<sel_bf16, ADD>(pool, slots, qsrc, qtok, row_add, add_rows, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C,
+                                               T, Smax, st);
+  }
+  return -1;
 }
 
 extern "C" int mq_bank_select_fwd(const float* pool, const int* slots, const int* qsrc, const int* qtok, void* vision, int* idx, int pool_rows,
                                   int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int out_type, void* stream) {
-  if (I <= 0) return 0;
-  if (Q <= 0 || MT <= 0 || S < 1 || S > 8 || C <= 0 || T <= 0 || Smax <= 0 || pool_rows < 0 || num_labels < 0 || cap < 0) return -1;
-  if ((long)Q * MT > 0x7fffffffL) return -1;
-  const hipStream_t st = (hipStream_t)stream;
-  switch (out_type) {
-    case 0: return bank_select_launch<float>(pool, slots, qsrc, qtok, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, st);
-    case 1: return bank_select_launch<_Float16>(pool, slots, qsrc, qtok, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, st);
-    case 2: return bank_select_launch<sel_bf16>(pool, slots, qsrc, qtok, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, st);
-  }
-  return -1;
+  return bank_select_any<false>(pool, slots, qsrc, qtok, nullptr, 0, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax, out_type,
+                                stream);
+}
+
+extern "C" int mq_bank_select_add_fwd(const float* pool, const int* slots, const int* qsrc, const int* qtok, const float* row_add, int add_rows,
+                                      void* vision, int* idx, int pool_rows, int num_labels, int cap, int I, int Q, int MT, int S, int C, int T,
+                                      int Smax, int out_type, void* stream) {
+  return bank_select_any<true>(pool, slots, qsrc, qtok, row_add, add_rows, vision, idx, pool_rows, num_labels, cap, I, Q, MT, S, C, T, Smax,
+                               out_type, stream);
 }
 
 #endif

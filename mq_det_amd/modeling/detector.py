@@ -22,7 +22,7 @@ from ..structures import BoxList, to_image_list
 from . import pipeline
 from .device_model import DeviceModel, compute_dtype  # noqa: F401  (compute_dtype: re-exported)
 from .graph_runner import Memo
-from .params import Container, build_param_tree
+from .params import PROMPT_OFFSET_ROWS, Container, build_param_tree
 from .query_selector import (build_item_token_index, build_token_index, consume_text_dropout_draws, prepare_positive_map,
                              text_dropout_mask, text_dropout_rate)
 
@@ -120,6 +120,9 @@ class GeneralizedVLRCNN_New(DeviceModel):
             # only the MDETR-style _v2 (:795-824) adds POWER; anything else raises NotImplementedError there too
             raise NotImplementedError(f"MODEL.DYHEAD.SCORE_AGG = {agg}: MEAN / MAX / ONEHOT"
                                       + (" / POWER" if mdetr else " (POWER only with TEST.MDETR_STYLE_AGGREGATE_CLASS_NUM != -1)"))
+        if M.DYHEAD.FUSE_CONFIG.get("ADD_LINEAR_LAYER", False) and M.LANGUAGE_BACKBONE.MAX_QUERY_LEN > PROMPT_OFFSET_ROWS:
+            raise NotImplementedError(f"MODEL.DYHEAD.FUSE_CONFIG.ADD_LINEAR_LAYER: rpn.tunable_linear holds {PROMPT_OFFSET_ROWS} token "
+                                      "positions, MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN is larger")
         if M.LANGUAGE_BACKBONE.MAX_QUERY_LEN > 256 or M.LANGUAGE_BACKBONE.MAX_QUERY_LEN % 8:
             raise NotImplementedError("MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN must be a multiple of 8 and <= 256 (VLFuse kernels)")
         if M.BACKBONE.OUT_CHANNELS != 256 or M.DYHEAD.CHANNELS != 256:
@@ -285,6 +288,7 @@ class GeneralizedVLRCNN_New(DeviceModel):
                                           side_ok=bool(_ops.KERNELS["LANG_SIDE_STREAMS"] == 1 and feats[0].is_cuda
                                                        and cfg.MODEL.DYHEAD.get("LEVEL_STREAMS", True) and not want_raw))
         lang["max_kv"] = max_kv
+        pipeline.prompt_offset(P, lang)                           # the tuned prompt of a fine-tuned checkpoint (ADD_LINEAR_LAYER); else nothing
         trace = [] if want_raw else None                          # raw mode: per-layer tensors, single-stream schedule
         head = pipeline.vldyhead(P, cfg, feats, lang, trace=trace)
         anchors = self._anchors(feats)
@@ -393,6 +397,7 @@ class GeneralizedVLRCNN_New(DeviceModel):
                 langs[m] = pipeline.language_backbone(P, cfg, args[m]["ids"], args[m]["am"], args[m]["vision"], pooled, args[m]["idx"],
                                                       want_gates=False, front=fronts[m], max_kv=max_kv)
                 langs[m]["max_kv"] = max_kv
+                pipeline.prompt_offset(P, langs[m])
             hold.append((f, pooled, fronts[m], langs[m]))
         anchors = self._anchors(feats[0])
         for m in range(n):

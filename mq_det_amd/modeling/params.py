@@ -21,6 +21,9 @@ import torch
 from torch import nn
 
 
+PROMPT_OFFSET_ROWS = 1000        # rows of rpn.tunable_linear.weight (MODEL.DYHEAD.FUSE_CONFIG.ADD_LINEAR_LAYER)
+
+
 def rel_pos_index(ws):
     ys, xs = torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")
     pos = torch.stack([ys.reshape(-1), xs.reshape(-1)])
@@ -228,6 +231,10 @@ def param_specs(cfg):
     yield p + ".bias0", (1,), f"const:{prior}"
     for l in range(5):
         yield f"{p}.scales.{l}.scale", (1,), "one"
+    if D.FUSE_CONFIG.get("ADD_LINEAR_LAYER", False):
+        # the tuned prompt of a fine-tuned checkpoint (vldyhead.py:929-931: nn.Linear(lang_dim, 1000, bias=False), zero): row t is added to
+        # the language features of token position t in front of the head (:955-958)
+        yield "rpn.tunable_linear.weight", (PROMPT_OFFSET_ROWS, H), "zero"
     for l, (s, a) in enumerate(zip(M.RPN.ANCHOR_STRIDE, M.RPN.ANCHOR_SIZES)):
         yield f"rpn.anchor_generator.cell_anchors.{l}", (1, 4), f"buf:anchor:{s}:{a}"
 

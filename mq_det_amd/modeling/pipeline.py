@@ -127,7 +127,7 @@ def build_plan(sd, cfg, device, dtype=torch.float16):
     def f32(name):
         return sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
     for k, v in sd.items():
-        if v.dtype.is_floating_point:
+        if v.dtype.is_floating_point and not k.startswith("query_selector."):         # (a fine-tuned selector's state stays with the selector)
             P[k] = v.detach().to(device=device, dtype=dtype).contiguous()
     _pack_swin(P, sd, M.SWINT, "backbone.body", device, dtype)
     # convs: channels_last weights
@@ -222,6 +222,8 @@ def build_plan(sd, cfg, device, dtype=torch.float16):
     P["rpn.head.inv_scale"] = float(math.exp(-float(sd["rpn.head.log_scale"])))
     for l in range(5):
         P[f"anchors.cell.{l}"] = f32(f"rpn.anchor_generator.cell_anchors.{l}")
+    if "rpn.tunable_linear.weight" in sd:                 # MODEL.DYHEAD.FUSE_CONFIG.ADD_LINEAR_LAYER: the addend of prompt_offset, unrounded
+        P["rpn.tunable_linear.w32"] = f32("rpn.tunable_linear.weight")
     return P
 
 
@@ -633,6 +635,27 @@ def language_backbone(P, cfg, input_ids, attention_mask, vision, images, idx, wa
     aggregate = embedded.sum(1) / attention_mask.sum(-1, keepdim=True).float()
     return {"aggregate": aggregate, "embedded": embedded, "masks": attention_mask, "hidden": x, "hidden32": x32,
             "key_bias": key_bias, "kv_len": kv_len, "vision_query_gates": gates, "augmented_vision": vision}
+
+
+def prompt_offset(P, lang):
+    """MODEL.DYHEAD.FUSE_CONFIG.ADD_LINEAR_LAYER (vldyhead.py:955-958): `tunable_linear.weight[:T]` added to the language features in front
+    of the head -- `embedded`, `hidden` and the unrounded `hidden32` -- in place in `lang`.  Without the parameter in the plan: nothing.
+    Row t of the weight belongs to token position t.  The device programs run on the first T_live positions of the caption (live-row
+    compaction, detector._live_len, keeps the FIRST positions), so W[:T_live] is the reference's W[:T] cut to the rows that exist here.
+    One fp32 sum, one rounding to the operand type: where the unrounded stream exists the 16-bit operand is rounded from ITS sum."""
+    w = P.get("rpn.tunable_linear.w32")
+    if w is None:
+        return lang
+    T = lang["hidden"].shape[1]
+    w = w[:T]
+    lang["embedded"] = lang["embedded"] + w
+    h32 = lang.get("hidden32")
+    if h32 is not None:
+        h32 = lang["hidden32"] = h32 + w
+        lang["hidden"] = h32.to(lang["hidden"].dtype)
+    else:
+        lang["hidden"] = (lang["hidden"].float() + w).to(lang["hidden"].dtype)
+    return lang
 
 
 # ----------------------------------------------------------------------------- VLDyHead

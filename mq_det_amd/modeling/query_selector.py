@@ -8,6 +8,9 @@ EACH of the 6 GCP layers (modeling_bert_new.py:40-63,162-184); it is built once,
 positive_map the caller already holds -- no device work, no sync.
 With a device-resident `QueryBank` (mq_det_amd.query_bank) instead of the dict, the draws stay on the host and the rows and the index come
 from one kernel launch (`_select_resident`, csrc/query_bank.hip mq_bank_select_fwd).
+Fine-tuned checkpoints (DESIGN.md "Fine-tuned checkpoints"): VISION_QUERY.LEARNABLE_BANK keeps the bank as the reference's `nn.ParameterDict`
+`query_bank.<label>` (:17-21, 59-60) and VISION_QUERY.ADD_VISION_LAYER owns `tunable_vision_linear.weight` [1000, C], added to an image's
+concatenated query rows before the padding (:98-99) -- on the resident path inside the same launch (mq_bank_select_add_fwd).
 """
 import os
 import random
@@ -18,6 +21,9 @@ from torch import nn
 
 from .. import ops as _ops
 from ..query_bank import QueryBank
+from .params import Container
+
+VISION_LAYER_ROWS = 1000                                       # rows of `tunable_vision_linear.weight` (query_selector.py:27)
 
 
 def labels_and_maps(positive_map, T, device="cpu", dtype=torch.float32):
@@ -140,33 +146,130 @@ class QuerySelector(nn.Module):
         # skipped and memoised (same selections, no per-forward host work), and the generator state then differs from a
         # reference run's as soon as one caption did not need a real draw.
         self.reference_rng = bool(cfg.VISION_QUERY.get("REFERENCE_RNG_STREAM", False))
+        # fine-tuned state (both off in every shipped yaml: nothing below exists then and the selector is what it was)
+        self.learnable_bank = bool(cfg.VISION_QUERY.get("LEARNABLE_BANK", False))
+        self.add_vision_layer = bool(cfg.VISION_QUERY.get("ADD_VISION_LAYER", False))
         self.query_bank = None
+        self._loaded = None                                    # what `load_query_bank` handed over while the bank is a ParameterDict
+        self._param_bank = None                                # {int(label): tensor} view of the ParameterDict (dropped with the memos)
         self._snapshot = None                                  # host counts of a resident QueryBank at load time (None: dict bank)
         self._dev_bank = {}
         self._sel_cache = {}
+        if self.learnable_bank or self.add_vision_layer:
+            self._register_load_state_dict_pre_hook(self._adopt_checkpoint_state)
         path = cfg.VISION_QUERY.QUERY_BANK_PATH
         if path:
             if not os.path.exists(path):
                 raise FileNotFoundError(f"query bank path {path} not exists")
-            self.load_query_bank(path)
+            if self.learnable_bank:
+                self._make_learnable_bank(torch.load(path, map_location="cpu"))
+                self._make_vision_layer()
+            else:
+                self.load_query_bank(path)
+
+    # ------------------------------------------------------------------ fine-tuned state
+    def _make_learnable_bank(self, tensors):
+        """The bank as parameters, named like the reference's (:20): `query_bank.<label>` [n, scales, C], frozen."""
+        prev = self.__dict__.get("query_bank")
+        bank = nn.ParameterDict({str(k): nn.Parameter(v.detach().clone(), requires_grad=False) for k, v in tensors.items()
+                                 if torch.is_tensor(v)})       # (an entry without rows stays a key of the state dict; it selects nothing)
+        self.query_bank = bank                                  # (nn.Module.__setattr__ takes the plain attribute away)
+        if prev is not None:                                    # a bank loaded before the parameters existed stays what is selected from
+            self._loaded = prev
+        self._drop_memos()
+
+    def _make_vision_layer(self, width=None):
+        """`tunable_vision_linear.weight` [1000, C], zero like the reference's (:27-28); C from the bank unless given.  Does nothing without
+        the key, when the parameter exists, or while no width is known."""
+        if not self.add_vision_layer or "tunable_vision_linear" in self._modules:
+            return
+        if width is None:
+            if not self._has_rows():
+                return
+            width = self._width()
+        self.tunable_vision_linear = Container()
+        self.tunable_vision_linear.register_parameter(
+            "weight", nn.Parameter(torch.zeros(VISION_LAYER_ROWS, int(width), dtype=torch.float32), requires_grad=False))
+
+    def _has_rows(self):
+        bank = self._source()
+        if isinstance(bank, QueryBank):
+            return bank.pool is not None
+        return bank is not None and any(torch.is_tensor(v) and v.numel() for v in bank.values())
+
+    def _adopt_checkpoint_state(self, state_dict, prefix, *_):
+        """load_state_dict pre-hook: a checkpoint alone is enough.  The parameters this selector does not own yet are created from the
+        incoming keys `query_bank.<label>` / `tunable_vision_linear.weight` with their shapes (the reference needs the original bank
+        file for that, :17-28); they are filled by the load that follows.  The memos of rows that depend on parameters are dropped."""
+        if self.learnable_bank and not isinstance(self._modules.get("query_bank"), nn.ParameterDict):
+            p = prefix + "query_bank."
+            found = {k[len(p):]: v for k, v in state_dict.items() if k.startswith(p) and torch.is_tensor(v)}
+            if found:
+                self._make_learnable_bank(found)
+        key = prefix + "tunable_vision_linear.weight"
+        if key in state_dict and torch.is_tensor(state_dict[key]) and state_dict[key].dim() == 2:
+            self._make_vision_layer(state_dict[key].shape[1])
+        self._drop_memos()
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._drop_memos()
+        return out
+
+    def _drop_memos(self):
+        self._param_bank = None
+        self._dev_bank = {}
+        self._sel_cache = {}
+
+    def _source(self):
+        """The bank the selection reads: what `load_query_bank` handed over last; else the learnable parameters as the plain dict
+        `{int(label): tensor}` (same draws, same order, a label without an entry is text-only); else `query_bank` as it is."""
+        if self._loaded is not None:
+            return self._loaded
+        bank = self.query_bank
+        if isinstance(bank, nn.ParameterDict):
+            if self._param_bank is None:
+                self._param_bank = {int(k): v.detach() for k, v in bank.items()}
+            return self._param_bank
+        return bank
+
+    def _row_add(self, n_rows, device):
+        """`tunable_vision_linear.weight` (fp32, on `device`) for items of up to `n_rows` real vision rows; None without the key.  Row v of
+        the weight belongs to position v of an item's concatenated rows, v = q * scales + s (query_selector.py:98-99)."""
+        if not self.add_vision_layer or "tunable_vision_linear" not in self._modules:
+            return None
+        w = self.tunable_vision_linear.weight
+        if n_rows > w.shape[0]:
+            # the reference fails on the shape mismatch of the sum at this point
+            raise ValueError(f"VISION_QUERY.ADD_VISION_LAYER: an item holds {n_rows} vision-query rows, tunable_vision_linear has {w.shape[0]}")
+        key = ("row_add", str(device))
+        if key not in self._dev_bank:
+            self._dev_bank[key] = w.detach().to(device=device, dtype=torch.float32).contiguous()
+        return self._dev_bank[key]
 
     def load_query_bank(self, bank):
         """`bank`: path to a torch-saved dict or the dict itself: {label: Tensor[n, scales, C]}, or a device-resident `QueryBank`.
         A `QueryBank` is kept as it is, with a host SNAPSHOT of its counts: its pool and slot table are append-only, so the rows the
         snapshot names stay where they are whatever is admitted later (also across a reallocation: the bank's current tensors are read at
-        every call), and rows admitted after this call stay invisible until the bank is loaded again."""
-        if isinstance(bank, QueryBank):
-            self.query_bank, self._snapshot = bank, (bank, list(bank._counts()))
+        every call), and rows admitted after this call stay invisible until the bank is loaded again.
+        With VISION_QUERY.LEARNABLE_BANK / ADD_VISION_LAYER the reference asserts that this is never called (:34-35).  Here it stays allowed
+        and replaces what the selector selects FROM; the parameters `query_bank.<label>` stay in the state dict as they are, and
+        `tunable_vision_linear.weight` is created at the first call when no checkpoint or bank file gave its width before."""
+        if not isinstance(bank, QueryBank):
+            bank = torch.load(bank, map_location="cpu") if isinstance(bank, (str, os.PathLike)) else bank
+        if isinstance(self._modules.get("query_bank"), nn.ParameterDict):
+            self._loaded = bank
         else:
-            self.query_bank = torch.load(bank, map_location="cpu") if isinstance(bank, (str, os.PathLike)) else bank
-            self._snapshot = None
+            self.query_bank = bank
+        self._snapshot = (bank, list(bank._counts())) if isinstance(bank, QueryBank) else None
         self._dev_bank = {}
         self._sel_cache = {}
+        self._make_vision_layer()
 
     def _resident(self):
         """The counts snapshot of a resident `QueryBank`; None with a dict bank or none.  (A `QueryBank` assigned to `query_bank` without
         `load_query_bank` is snapshotted at its first use.)"""
-        bank = self.query_bank
+        bank = self._source()
         if not isinstance(bank, QueryBank):
             return None
         if self._snapshot is None or self._snapshot[0] is not bank:
@@ -182,7 +285,7 @@ class QuerySelector(nn.Module):
         """Bank entry of a label; None when the label has no vision query.  Reference banks are `defaultdict(list)`
         (engine/inference.py:401): a label without queries reads as `[]` and contributes no vision rows
         (query_selector.py:77-78, `isinstance(candidate_queries, list)`); a plain dict without the key is treated alike."""
-        bank = self.query_bank
+        bank = self._source()
         cand = bank[label] if (label in bank or hasattr(bank, "default_factory")) else None
         if cand is None or isinstance(cand, (list, tuple)) or len(cand) == 0:
             return None
@@ -218,7 +321,7 @@ class QuerySelector(nn.Module):
             pos = self._draw(self._count(label), draw)
             if len(pos) == 0:
                 return None
-            bank = self.query_bank
+            bank = self._source()
             rows = bank.slots[label].index_select(0, torch.from_numpy(pos).to(bank.slots.device)).long()
             return bank.pool[rows].flatten(0, 1).to(device=device, dtype=dtype)
         cand = self._candidates(label)
@@ -247,8 +350,8 @@ class QuerySelector(nn.Module):
 
     def _width(self):
         if self._resident() is not None:
-            return 1 if self.query_bank.pool is None else self.query_bank.pool.shape[-1]
-        for v in self.query_bank.values():
+            return 1 if self._source().pool is None else self._source().pool.shape[-1]
+        for v in self._source().values():
             if torch.is_tensor(v) and v.numel():
                 return v.shape[-1]
         return 1
@@ -259,19 +362,26 @@ class QuerySelector(nn.Module):
         if self._resident() is not None:
             return self._select_resident(batched_labels, batched_positive_maps, T, device, dtype)
         per_image, tok_lists = [], []
+        # ADD_VISION_LAYER: the rows are assembled in fp32, the offset is added, and the sum is rounded ONCE (the per-label cache in `dtype`
+        # would round twice)
+        add = self.add_vision_layer and "tunable_vision_linear" in self._modules
+        row_dtype = torch.float32 if add else dtype
         for labels, pmap in zip(batched_labels, batched_positive_maps):
             rows, owners = [], [[] for _ in range(T)]
             base = 0
             draw = not self.deterministic(labels)
             for lab in labels:
-                r = self._rows(lab, device, dtype, draw)
+                r = self._rows(lab, device, row_dtype, draw)
                 if r is None:
                     continue
                 rows.append(r)
                 for t in pmap[lab]:
                     owners[t].extend(range(base, base + r.shape[0]))
                 base += r.shape[0]
-            per_image.append(torch.cat(rows) if rows else torch.zeros(0, self._width(), device=device, dtype=dtype))
+            if add and rows:
+                per_image.append((torch.cat(rows) + self._row_add(base, device)[:base]).to(dtype))
+            else:
+                per_image.append(torch.cat(rows) if rows else torch.zeros(0, self._width(), device=device, dtype=dtype))
             tok_lists.append(owners)
         vision = torch.nn.utils.rnn.pad_sequence(per_image, batch_first=True)
         S = max(1, max(len(o) for owners in tok_lists for o in owners))
@@ -287,7 +397,7 @@ class QuerySelector(nn.Module):
         two integer tables built with numpy -- qsrc [I, Q, 2] = (label, position in the label's slot row) and qtok [I, Q, MT] = the label's
         token positions per selected query, -1 padded --, ONE upload and ONE launch (ops.bank_select) that writes the padded vision rows in
         `dtype` and the gather index.  No per-label copies, no torch.cat / pad_sequence, no loop over the T token positions."""
-        bank, I = self.query_bank, len(batched_labels)
+        bank, I = self._source(), len(batched_labels)
         e_item, e_lab, e_tok, e_pos = [], [], [], []              # one entry per (item, label with rows)
         toks, tok_of = [], {}                                     # distinct token lists of this call: (id(map), label) -> row of tokU
         snap, k = self._resident(), self.num_query_per_class
@@ -321,6 +431,7 @@ class QuerySelector(nn.Module):
         e_n = np.asarray([len(p) for p in e_pos])
         per_item = np.bincount(e_item, weights=e_n, minlength=I).astype(np.int64)
         Q, MT = int(per_item.max()), max(1, max(len(t) for t in toks))
+        row_add = self._row_add(Q * S, bank.pool.device)          # (refuses an item with more rows than the offset has, before the launch)
         tokU = np.full((len(toks), MT), -1, dtype=np.int32)
         for u, t in enumerate(toks):
             tokU[u, :len(t)] = t
@@ -340,7 +451,11 @@ class QuerySelector(nn.Module):
         np.add.at(owners, (e_item[:, None] * T + tokE)[live], np.broadcast_to((e_n * S)[:, None], tokE.shape)[live])
         smax = max(1, int(owners.max()))
         dev_tab = torch.from_numpy(tab).to(bank.pool.device, non_blocking=True)
-        vision, idx = _ops.bank_select(bank.pool, bank.slots, dev_tab[:I * Q * 2].view(I, Q, 2), dev_tab[I * Q * 2:].view(I, Q, MT), T, smax, dtype)
+        if row_add is None:
+            vision, idx = _ops.bank_select(bank.pool, bank.slots, dev_tab[:I * Q * 2].view(I, Q, 2), dev_tab[I * Q * 2:].view(I, Q, MT), T, smax, dtype)
+        else:
+            vision, idx = _ops.bank_select(bank.pool, bank.slots, dev_tab[:I * Q * 2].view(I, Q, 2), dev_tab[I * Q * 2:].view(I, Q, MT), T, smax, dtype,
+                                           row_add=row_add)
         return vision.to(device), idx.to(device)
 
     def select_cached(self, key, labels, positive_map, B, T, device, dtype):
@@ -358,21 +473,26 @@ class QuerySelector(nn.Module):
 
     def forward(self, batched_label_list, batched_location_map, batched_pos_labels=None):
         """Reference-compatible output (queries, 0/1 attention masks [B,V,T], has_vision_query)."""
-        if self.query_bank is None:
+        if self._source() is None:
             return None, None, None
         qs, ms, has = [], [], []
         for labels, maps in zip(batched_label_list, batched_location_map):
             q_img, m_img = [], []
             flags = []
             draw = not self.deterministic(labels)
+            add = self.add_vision_layer and "tunable_vision_linear" in self._modules
             for lab, loc in zip(labels, maps):
-                r = self._rows(lab, loc.device, loc.dtype, draw)
+                r = self._rows(lab, loc.device, torch.float32 if add else loc.dtype, draw)
                 flags.append(0 if r is None else 1)
                 if r is None:
                     continue
                 q_img.append(r)
                 m_img.append(loc[None].expand(r.shape[0], -1))
-            qs.append(torch.cat(q_img))
+            if add and q_img:
+                q = torch.cat(q_img)
+                qs.append((q + self._row_add(len(q), q.device)[:len(q)]).to(m_img[0].dtype))
+            else:
+                qs.append(torch.cat(q_img))
             ms.append(torch.cat(m_img))
             has.append(flags)
         q = torch.nn.utils.rnn.pad_sequence(qs, batch_first=True)

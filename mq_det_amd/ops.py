@@ -84,6 +84,7 @@ _SIGNATURES = {
     "mq_flickr_tally": (_i, [_vp] * 5 + [_i, _i, _i, _vp]),
     "mq_bank_admit": (_i, [_vp] * 8 + [_i] * 8 + [_f, _vp]),
     "mq_bank_select_fwd": (_i, [_vp] * 6 + [_i] * 11 + [_vp]),
+    "mq_bank_select_add_fwd": (_i, [_vp] * 5 + [_i] + [_vp] * 2 + [_i] * 11 + [_vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
@@ -1887,21 +1888,31 @@ def bank_admit(cand, sorted_labels, order, pool, inv_norm, slots, counts, state,
 _SELECT_OUT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
-def bank_select(pool, slots, qsrc, qtok, T, smax, dtype):
+def bank_select(pool, slots, qsrc, qtok, T, smax, dtype, row_add=None):
     """The vision queries of a forward from a resident bank, one launch: pool [R, S, C] fp32, slots [labels, cap] int32, qsrc [I, Q, 2] and
     qtok [I, Q, MT] int32 (include/mqdet_hip.h mq_bank_select_fwd) -> vision [I, Q * S, C] `dtype` (fp32 / fp16 / bf16, padding rows zero),
-    idx [I, T, smax] int32 (-1 padded)."""
+    idx [I, T, smax] int32 (-1 padded).
+    row_add [rows, C] fp32 (VISION_QUERY.ADD_VISION_LAYER; mq_bank_select_add_fwd): row v of an item that names a bank row is
+    round(fp32(bank row) + row_add[v]); the caller has checked that no item holds more than `rows` real rows.  None: mq_bank_select_fwd."""
     lib = load_library()
-    _need_gpu(pool, slots, qsrc, qtok)
+    _need_gpu(pool, slots, qsrc, qtok, row_add)
     assert pool.dtype == torch.float32 and pool.dim() == 3 and slots.dtype == qsrc.dtype == qtok.dtype == torch.int32 and slots.dim() == 2
     for t in (pool, slots, qsrc, qtok):
         assert t.is_contiguous()
     R, S, C = pool.shape
     I, Q, MT = qtok.shape
     assert qsrc.shape == (I, Q, 2) and I > 0 and Q > 0 and MT > 0 and 1 <= S <= 8 and T > 0 and smax > 0
+    if row_add is not None:
+        assert row_add.dtype == torch.float32 and row_add.dim() == 2 and row_add.shape[1] == C and row_add.is_contiguous()
     vision = torch.empty(I, Q * S, C, dtype=dtype, device=pool.device)
     idx = torch.empty(I, int(T), int(smax), dtype=torch.int32, device=pool.device)
-    with _timed("bank_select", I * Q * S * C * (4 + vision.element_size()) + idx.numel() * 4):
-        _chk(lib.mq_bank_select_fwd(_ptr(pool), _ptr(slots), _ptr(qsrc), _ptr(qtok), _ptr(vision), _ptr(idx), R, slots.shape[0], slots.shape[1],
-                                    I, Q, MT, S, C, int(T), int(smax), _SELECT_OUT[dtype], _stream()), "mq_bank_select_fwd")
+    if row_add is None:
+        with _timed("bank_select", I * Q * S * C * (4 + vision.element_size()) + idx.numel() * 4):
+            _chk(lib.mq_bank_select_fwd(_ptr(pool), _ptr(slots), _ptr(qsrc), _ptr(qtok), _ptr(vision), _ptr(idx), R, slots.shape[0], slots.shape[1],
+                                        I, Q, MT, S, C, int(T), int(smax), _SELECT_OUT[dtype], _stream()), "mq_bank_select_fwd")
+        return vision, idx
+    with _timed("bank_select", I * Q * S * C * (8 + vision.element_size()) + idx.numel() * 4):
+        _chk(lib.mq_bank_select_add_fwd(_ptr(pool), _ptr(slots), _ptr(qsrc), _ptr(qtok), _ptr(row_add), row_add.shape[0], _ptr(vision), _ptr(idx),
+                                        R, slots.shape[0], slots.shape[1], I, Q, MT, S, C, int(T), int(smax), _SELECT_OUT[dtype], _stream()),
+             "mq_bank_select_add_fwd")
     return vision, idx

@@ -168,6 +168,12 @@ class QueryBank:
         return bank
 
     @classmethod
+    def from_state_dict(cls, sd, device="cuda", prefix="query_selector.query_bank."):
+        """A resident bank from the learnable bank of a fine-tuned checkpoint (VISION_QUERY.LEARNABLE_BANK): the entries
+        `<prefix><label>` of the state dict `sd`, in its order."""
+        return cls.from_dict({int(k[len(prefix):]): v.detach().float() for k, v in sd.items() if k.startswith(prefix)}, device)
+
+    @classmethod
     def load(cls, path, device="cuda"):
         return cls.from_dict(load_bank_file(path, device), device)
 
