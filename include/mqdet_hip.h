@@ -597,6 +597,24 @@ int mq_bank_select_add_fwd(const float* pool, const int* slots, const int* qsrc,
                            int* idx, int pool_rows, int num_labels, int cap, int I, int Q, int MT, int S, int C, int T, int Smax, int out_type,
                            void* stream);
 
+/* ---- Evaluator rows from a forward's packed detections (csrc/eval_rows.hip, host side mq_det_amd/evaluation.py update_packed).  fp32 / integer data only.
+ * packed [items, K2, 6] fp32 (x1, y1, x2, y2, score, label) and counts [items] int32 as `_rest_program` leaves them: low 16 bits = live rows and
+ * bit 16 = tie overflow, or -- flags bit 0, candidate mode -- the plain count; a count above K2 is read as K2.  table [E, 5] int32, one entry per
+ * source item in OUTPUT order: (item, 1 on the first entry of an image, image id, ratio_w, ratio_h), the last three as the bits of an fp32;
+ * entry 0 starts an image whatever its mark says.  lbl_keys [n_lbl] int32 sorted / lbl_vals [n_lbl] fp32: the category of a row is
+ * lbl_vals[j] where lbl_keys[j] == (int)label, NaN where no key matches (n_lbl = 0: every row); n_lbl < 0: no table, the label itself.
+ * -> rows [capacity, cols] fp32, cols 7 or 8: (image id, category, score, x1 * ratio_w, y1 * ratio_h, x2 * ratio_w - x1 * ratio_w,
+ *   y2 * ratio_h - y1 * ratio_h [, 1 on the first row of an image, 0 elsewhere]), every operation rounded by itself (no contraction), width and
+ *   height + 1 with flags bit 1; the live rows of the entries in table order, dense from row 0.  flags bit 2: an image whose entries hold no
+ *   live row emits (image id, NaN, 0, 0, 0, 0, 0, 1).  n_rows [1] int32 = rows written, overflow [1] int32 = OR of the bit 16 seen.
+ *   capacity >= E * K2 (+ images with flags bit 2) holds every row; no row at or beyond it is written and rows behind the last are untouched.
+ * One launch, no host sync, no allocation.  An entry whose item lies outside [0, items) contributes no rows; table_host (may be NULL) is the
+ * host's copy of the table: with it such an entry returns -2 before the launch.  -1: bad sizes.
+ * Replaces, per forward, engine/inference.py:643-648 (resize_box, the LVIS tuple), :680-686 (the COCO concatenation) and the row building of
+ * LvisEvaluatorFixedAP.update / prepare_for_coco_detection (convert_to_xywh, convert("xywh"), the label map). */
+int mq_eval_rows(const float* packed, const int* counts, const int* table, const int* table_host, const int* lbl_keys, const float* lbl_vals,
+                 int n_lbl, float* rows, int* n_rows, int* overflow, int E, int items, int K2, int cols, long capacity, int flags, void* stream);
+
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --
  *     packed[((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8] = W[n][k]

@@ -17,7 +17,9 @@ Image ids must be exactly representable in fp32 (< 2^24; LVIS / COCO ids are < 6
 
 `LvisFixedAPEvaluator` computes the LVIS Fixed AP from that state on the device (csrc/lvis_eval.hip; DESIGN.md "LVIS Fixed AP").
 `CocoAPEvaluator` computes pycocotools' COCO AP (COCO / ODinW) from rows of the same kind (csrc/coco_eval.hip; DESIGN.md "COCO AP").
-`FlickrRecallEvaluator` computes Flickr30k Entities Recall@k (phrase grounding) from such rows (csrc/flickr_eval.hip; DESIGN.md "Phrase grounding")."""
+`FlickrRecallEvaluator` computes Flickr30k Entities Recall@k (phrase grounding) from such rows (csrc/flickr_eval.hip; DESIGN.md "Phrase grounding").
+`update_packed` of the first two takes a forward's packed detections as they lie on the device: csrc/eval_rows.hip builds the rows in one launch and
+`append_block` keeps them with their device count until the next fold (mq_det_amd/detection.py; DESIGN.md "Detection evaluation loop")."""
 import json
 import math
 import os
@@ -68,8 +70,24 @@ class FixedAPAccumulator:
         xywh = torch.stack((b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]), 1) if n else b.reshape(0, 4)
         self.update(torch.full((n,), float(image_id)), boxlist.get_field("labels"), boxlist.get_field("scores"), xywh)
 
+    def append_block(self, rows_buffer, n_rows_dev):
+        """Rows that were built on the device (ops.eval_rows): the buffer [capacity, columns] is kept whole together with the device int that
+        says how many of its rows are live; `_fold()` reads the pending counts at once.  Towards the prune trigger a block weighs its capacity,
+        the number the host knows."""
+        if rows_buffer.dim() != 2 or rows_buffer.shape[1] != self.rows.shape[1] or rows_buffer.dtype != torch.float32:
+            raise ValueError(f"append_block: rows of shape [n, {self.rows.shape[1]}] fp32 expected, got {tuple(rows_buffer.shape)} {rows_buffer.dtype}")
+        self._pending.append((rows_buffer, n_rows_dev.reshape(())))
+        self._npending += len(rows_buffer)
+        limit = self.prune_at if self.prune_at is not None else 4 * max(len(self.rows), 1 << 16)
+        if self._npending >= limit:
+            self._fold()
+
     def _fold(self):
         if self._pending:
+            blocks = [p for p in self._pending if isinstance(p, tuple)]
+            if blocks:                                         # every pending block's row count in ONE device->host read
+                live = iter(torch.stack([n for _, n in blocks]).tolist())
+                self._pending = [p[0][:max(0, min(int(next(live)), len(p[0])))] if isinstance(p, tuple) else p for p in self._pending]
             self.rows = self._prune(torch.cat([self.rows] + self._pending))
             self._pending, self._npending = [], 0
 
@@ -117,6 +135,26 @@ class FixedAPAccumulator:
         return out
 
 
+def _packed_rows(ev, packed, counts, image_ids, n_chunks, candidate, cols, ratios, **mode):
+    """The launch both evaluators' `update_packed` share: entry table in image-major order out of the forward's chunk-major items (the B x g
+    permutation), a fresh row buffer of the full capacity, one ops.eval_rows; -> (rows buffer, state [2] int32 on the device: rows written,
+    overflow bit).  The overflow bit is folded into ev._tie_overflow on the device."""
+    from . import ops
+    ids = _ids(image_ids, "predictions.image_id")
+    B, g = len(ids), int(n_chunks)
+    if packed.dim() != 3 or packed.shape[0] != g * B or len(ratios) != B:
+        raise ValueError(f"update_packed: {B} images x {g} chunks, packed detections of shape {tuple(packed.shape)}, {len(ratios)} image sizes")
+    K2 = packed.shape[1]
+    table = ops.eval_rows_table([c * B + b for b in range(B) for c in range(g)], [float(i) for i in ids for _ in range(g)],
+                                [r[0] for r in ratios for _ in range(g)], [r[1] for r in ratios for _ in range(g)],
+                                [c == 0 for _ in range(B) for c in range(g)], g * B, ev.device)
+    rows = torch.empty(g * B * K2 + (B if mode.get("placeholder") else 0), cols, dtype=torch.float32, device=ev.device)
+    state = torch.empty(2, dtype=torch.int32, device=ev.device)
+    ops.eval_rows(packed.contiguous(), counts.contiguous(), table, rows, state, cols=cols, candidate=candidate, **mode)
+    ev._tie_overflow = state[1] if ev._tie_overflow is None else torch.maximum(ev._tie_overflow, state[1])
+    return rows, state
+
+
 # ====================================================================================================== LVIS Fixed AP on the device
 _ID_LIMIT = 1 << 24          # ids above are not exact in the accumulator's fp32 rows
 _AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
@@ -149,6 +187,7 @@ class LvisFixedAPEvaluator:
         self.device = torch.device(device)
         self.topk = int(topk)
         self.acc = FixedAPAccumulator(self.topk, self.device)
+        self._tie_overflow = None
         self.results = OrderedDict()
         self.eval = {}
         self.iou_thrs = np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1, endpoint=True)
@@ -227,8 +266,43 @@ class LvisFixedAPEvaluator:
             xywh = torch.stack((xmin, ymin, xmax - xmin, ymax - ymin), dim=1)
             self.acc.update(torch.full((n,), float(image_id)), pred["labels"], pred["scores"], xywh)
 
+    def update_packed(self, packed, counts, image_ids, input_sizes, orig_sizes, n_chunks, candidate=False):
+        """One launch group of `forward_chunks_packed` -- packed [g * B, K2, 6], the RAW counts [g * B] int32 on the device, items chunk-major
+        -- for the B images `image_ids` (original ids) and g = `n_chunks` chunks; input_sizes / orig_sizes: per image (height, width) of the
+        network input (`images.image_sizes`) and of the original image (the target's `orig_size`), host numbers.  The rows are those of
+        `update([(id, {...}) for every chunk])` after the engine's `resize_box` (engine/inference.py:643-648) run per image, image by image,
+        bit for bit and in the same order -- built by one launch of csrc/eval_rows.hip, without a host sync; the counts stay on the device
+        until the accumulator folds.  candidate: the counts are plain numbers (TEST.USE_MULTISCALE's candidate mode)."""
+        rows, state = _packed_rows(self, packed, counts, image_ids, n_chunks, candidate, cols=7,
+                                   ratios=[(float(ow) / float(iw), float(oh) / float(ih)) for (ih, iw), (oh, ow) in zip(input_sizes, orig_sizes)])
+        self.acc.append_block(rows, state[0])
+
+    def tie_overflow(self):
+        """Whether a forward that came through `update_packed` had more detections tied with the DETECTIONS_PER_IMG-th score than tie slots
+        (`last_tie_overflow` of the BoxList path).  One host sync."""
+        return self._tie_overflow is not None and bool(self._tie_overflow.item())
+
     def synchronize_between_processes(self):
         self.acc.synchronize_between_processes()
+
+    @staticmethod
+    def write_results(lines, path):
+        """`write_lvis_results` (engine/inference.py:354-366): bbox.csv from the strings of `summarize()`."""
+        out = ["metric, avg "]
+        for line in lines:
+            out.append(" ".join(line.split(" ")[:-2]) + ", " + line.split(" ")[-1] + " ")
+        with open(path, "w") as f:
+            f.write("\n".join(out) + "\n")
+
+    def save_instances_results(self, path):
+        """`LvisEvaluatorFixedAP.save_instances_results` (lvis_eval.py:877-884): the kept detections as one json list, sorted by image id
+        with Python's stable sort (within an image: the order of `acc.by_cat()`, categories ascending, scores descending)."""
+        instances = []
+        for _, inst in self.acc.by_cat().items():
+            instances = instances + inst
+        instances = sorted(instances, key=lambda x: x["image_id"], reverse=False)
+        with open(path, "w") as f:
+            json.dump(instances, f)
 
     def summarize(self):
         """Main process: the strings of LVISEval.print_results (max_dets = -1) and self.results; other ranks: None."""
@@ -386,6 +460,7 @@ class CocoAPEvaluator:
         ds = gt if isinstance(gt, dict) else gt.dataset
         self.device = torch.device(device)
         self.acc = _ResultRows(self.device)
+        self._tie_overflow = None
         self.results = OrderedDict()
         self.stats = []
         self.eval = {}
@@ -397,6 +472,7 @@ class CocoAPEvaluator:
         labels = sorted(label_to_cat_id)
         self.lbl_keys = torch.from_numpy(_ids(labels, "label_to_cat_id")).to(self.device)
         self.lbl_vals = torch.from_numpy(_ids([label_to_cat_id[k] for k in labels], "label_to_cat_id")).float().to(self.device)
+        self.lbl_keys32 = self.lbl_keys.to(torch.int32)          # (ids lie within +-2^24) the kernel's table
 
     # ------------------------------------------------------------------ ground truth, once
     def _ingest(self, ds):
@@ -473,6 +549,23 @@ class CocoAPEvaluator:
             r[:, 2] = bl.get_field("scores").to(dev).float()
             r[:, 3:7] = bl.convert("xywh").bbox
             self.acc.append(r)
+
+    def update_packed(self, packed, counts, image_ids, input_sizes, orig_sizes=None, n_chunks=1, candidate=False):
+        """One launch group of `forward_chunks_packed` -- packed [g * B, K2, 6], the RAW counts [g * B] int32 on the device, items chunk-major
+        -- for the B images `image_ids` (original ids) and g = `n_chunks` chunks; input_sizes: per image (height, width) of the network input
+        (`images.image_sizes`); orig_sizes is not read (the target size is the ground-truth image's, ratio 1 for an image the file lacks).
+        Per image one block holding its chunks in chunk order: the rows of `update({id: cat_boxlist([chunk outputs])})`, bit for bit and in
+        the same order, an image without a detection included -- built by one launch of csrc/eval_rows.hip, without a host sync."""
+        ids = _ids(image_ids, "predictions.image_id")
+        ratios = []
+        for i, (ih, iw) in zip(ids, input_sizes):
+            size = self.img_size.get(int(i))
+            ratios.append((1.0, 1.0) if size is None else (size[0] / float(iw), size[1] / float(ih)))
+        rows, state = _packed_rows(self, packed, counts, image_ids, n_chunks, candidate, cols=8, ratios=ratios, plus_one=True, placeholder=True,
+                                   lbl_keys=self.lbl_keys32, lbl_vals=self.lbl_vals)
+        self.acc.append_block(rows, state[0])
+
+    tie_overflow = LvisFixedAPEvaluator.tie_overflow
 
     def synchronize_between_processes(self, group=None, force=False):
         self.acc.synchronize_between_processes(group, force)

@@ -643,9 +643,36 @@ class GeneralizedVLRCNN_New(DeviceModel):
         if self.training:
             raise NotImplementedError("training forward is out of scope")
         images = to_image_list(images)
-        if self._use_vq() and 0.0 < text_dropout_rate(self.cfg) < 1.0:
+        if self._per_item_text_dropout():
             outs = [self.forward(images, captions=[cap] * images.tensors.shape[0], positive_map=pm) for cap, pm in chunks]
             return [o[0] if isinstance(o, tuple) else o for o in outs]
+        Bn = images.tensors.shape[0]
+        results = []
+        for packed, counts, g in self._chunk_groups(images, chunks, max_items):
+            counts = self._split_counts(counts.tolist())          # the one device->host sync of the group
+            for c in range(g):
+                results.append(self._boxlists(packed, counts, images.image_sizes, first=c * Bn))
+        return results
+
+    @torch.no_grad()
+    def forward_chunks_packed(self, images, chunks, max_items=32):
+        """`forward_chunks` without its host steps: per launch group (packed [g * B, K2, 6], RAW counts [g * B] int32 on the device, g), the
+        items chunk-major (item = chunk * B + image) -- what `LvisFixedAPEvaluator.update_packed` / `CocoAPEvaluator.update_packed` take.
+        Nothing is read back: no `.tolist()`, no BoxLists, and `last_tie_overflow` is not maintained (the overflow bit stays in the counts).
+        None with 0 < VISION_QUERY.TEXT_DROPOUT < 1, where `forward_chunks` loops `forward`: the caller then takes the BoxList path."""
+        if self.training:
+            raise NotImplementedError("training forward is out of scope")
+        images = to_image_list(images)
+        if self._per_item_text_dropout():
+            return None
+        return [(packed, counts.clone(), g) for packed, counts, g in self._chunk_groups(images, chunks, max_items)]
+
+    def _per_item_text_dropout(self):
+        return self._use_vq() and 0.0 < text_dropout_rate(self.cfg) < 1.0
+
+    def _chunk_groups(self, images, chunks, max_items):
+        """The launch groups of `forward_chunks`: yields (packed [g * B, K2, 6] -- a clone --, the group's raw counts as the program left them
+        -- under graph replay the graph's static buffer: read or clone before the next group runs --, g)."""
         dev = images.tensors.device
         feats, pooled = self._features(images)
         P, cfg = self._plan, self.cfg
@@ -655,7 +682,6 @@ class GeneralizedVLRCNN_New(DeviceModel):
         use_graph = self.use_hip_graph and not _ops.timing_active()
         im_wh = self._im_wh(images, dev)
         onehot = str(cfg.MODEL.DYHEAD.get("SCORE_AGG", "MEAN")).upper() == "ONEHOT"
-        results = []
         per = max(1, int(max_items) // Bn)
         for g0 in range(0, len(chunks), per):
             grp = chunks[g0:g0 + per]
@@ -696,11 +722,7 @@ class GeneralizedVLRCNN_New(DeviceModel):
             inputs = ([tile(f) for f in feats], None if pooled is None else pooled.repeat(g, 1, 1), front, rep(torch.cat(ids)),
                       rep(torch.cat(ams)), vision, idx, tok3, lab2, im_wh.repeat(g, 1), max(kvs))
             out = self._run("_rest_program", inputs, use_graph)
-            packed = out["packed"].clone()
-            counts = self._split_counts(out["counts"].tolist())
-            for c in range(g):
-                results.append(self._boxlists(packed, counts, images.image_sizes, first=c * Bn))
-        return results
+            yield out["packed"].clone(), out["counts"], g
 
 
 _DETECTION_META_ARCHITECTURES = {"GeneralizedVLRCNN_New": GeneralizedVLRCNN_New}

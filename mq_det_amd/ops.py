@@ -85,6 +85,7 @@ _SIGNATURES = {
     "mq_bank_admit": (_i, [_vp] * 8 + [_i] * 8 + [_f, _vp]),
     "mq_bank_select_fwd": (_i, [_vp] * 6 + [_i] * 11 + [_vp]),
     "mq_bank_select_add_fwd": (_i, [_vp] * 5 + [_i] + [_vp] * 2 + [_i] * 11 + [_vp]),
+    "mq_eval_rows": (_i, [_vp] * 6 + [_i] + [_vp] * 3 + [_i] * 4 + [_l, _i, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
@@ -1916,3 +1917,65 @@ def bank_select(pool, slots, qsrc, qtok, T, smax, dtype, row_add=None):
                                         R, slots.shape[0], slots.shape[1], I, Q, MT, S, C, int(T), int(smax), _SELECT_OUT[dtype], _stream()),
              "mq_bank_select_add_fwd")
     return vision, idx
+
+
+# ---- evaluator rows from a forward's packed detections (csrc/eval_rows.hip; host side: mq_det_amd/evaluation.py update_packed)
+EVAL_ROWS_CANDIDATE, EVAL_ROWS_PLUS_ONE, EVAL_ROWS_PLACEHOLDER = 1, 2, 4
+
+
+def eval_rows_table(entry_items, image_ids, ratio_w, ratio_h, first, n_items, device):
+    """The entry table of mq_eval_rows, one entry per source item in OUTPUT order: item index, image id (exact in fp32), the two fp32 resize
+    ratios, and 1 on the first entry of an image.  An item outside [0, n_items) is refused here, before anything is launched.  -> (table
+    [E, 5] int32 on `device`, its host copy); the upload is asynchronous from pinned memory on a GPU."""
+    import numpy as np
+    it = np.asarray(entry_items, dtype=np.int64).reshape(-1)
+    E = len(it)
+    if E == 0:
+        raise ValueError("eval_rows: an empty entry table")
+    if np.any(it < 0) or np.any(it >= int(n_items)):
+        bad = it[(it < 0) | (it >= int(n_items))][0]
+        raise ValueError(f"eval_rows: an entry names item {bad}, the forward has items 0 .. {int(n_items) - 1}")
+    host = np.empty((E, 5), dtype=np.int32)
+    host[:, 0] = it
+    host[:, 1] = np.asarray(first, dtype=bool).reshape(-1)
+    host[:, 2] = np.asarray(image_ids, dtype=np.float32).reshape(-1).view(np.int32)
+    host[:, 3] = np.asarray(ratio_w, dtype=np.float32).reshape(-1).view(np.int32)
+    host[:, 4] = np.asarray(ratio_h, dtype=np.float32).reshape(-1).view(np.int32)
+    t = torch.from_numpy(host)
+    device = torch.device(device)
+    if device.type == "cuda":
+        t = t.pin_memory()
+        return t.to(device, non_blocking=True), t
+    return t, t
+
+
+def eval_rows(packed, counts, table, rows, state, cols=7, candidate=False, plus_one=False, placeholder=False, lbl_keys=None, lbl_vals=None):
+    """One launch: the live detections of packed [items, K2, 6] / raw counts [items] -> rows (image id, category, score, x, y, w, h [, mark]) in the
+    order of `table` (eval_rows_table's pair), written into `rows` [capacity, cols] from row 0; state [2] int32 receives (rows written, tie-overflow
+    bit seen).  No host sync.  lbl_keys int32 sorted / lbl_vals fp32: the label table (an empty one gives NaN categories); None: the label itself.
+    Layouts: include/mqdet_hip.h mq_eval_rows."""
+    lib = load_library()
+    table, table_host = table
+    _need_gpu(packed, counts, table, rows, state, lbl_keys, lbl_vals)
+    assert packed.dtype == rows.dtype == torch.float32 and counts.dtype == table.dtype == state.dtype == torch.int32
+    assert packed.dim() == 3 and packed.shape[2] == 6 and cols in (7, 8) and rows.dim() == 2 and rows.shape[1] == cols and state.numel() == 2
+    for t in (packed, counts, table, rows, state):
+        assert t.is_contiguous()
+    items, K2 = packed.shape[:2]
+    E = len(table)
+    assert len(counts) == items and table.shape[1:] == (5,) and table_host.shape == table.shape and not table_host.is_cuda and E > 0 and K2 > 0
+    n_lbl = -1
+    if lbl_keys is not None:
+        assert lbl_keys.dtype == torch.int32 and lbl_vals.dtype == torch.float32 and lbl_keys.is_contiguous() and lbl_vals.is_contiguous()
+        n_lbl = len(lbl_keys)
+        assert len(lbl_vals) == n_lbl
+    images = int(table_host[:, 1].sum().item()) + int(table_host[0, 1].item() == 0)
+    capacity = len(rows)
+    if capacity < E * K2 + (images if placeholder else 0):
+        raise ValueError(f"eval_rows: {capacity} rows of room, {E} entries of {K2} rows{' and ' + str(images) + ' images' if placeholder else ''} need more")
+    flags = EVAL_ROWS_CANDIDATE * bool(candidate) + EVAL_ROWS_PLUS_ONE * bool(plus_one) + EVAL_ROWS_PLACEHOLDER * bool(placeholder)
+    # bytes: at most every packed row read and every output row written once, the counts and the table once per workgroup
+    with _timed("eval_rows", E * K2 * (24 + 4 * cols) + E * E * 24):
+        _chk(lib.mq_eval_rows(_ptr(packed), _ptr(counts), _ptr(table), ctypes.c_void_p(table_host.data_ptr()), _ptr(lbl_keys), _ptr(lbl_vals), n_lbl,
+                              _ptr(rows), _ptr(state), _ptr(state[1:]), E, items, K2, cols, capacity, flags, _stream()),
+             "mq_eval_rows")
