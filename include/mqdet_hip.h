@@ -519,7 +519,7 @@ int mq_tta_merge_finalize_special(const float* boxes_m, const float* scores_m, c
 int mq_tta_merge_nms(const float* boxes_s, const int* labels_s, const int* nvalid, const int* cls_rank, unsigned char* keep, float* ws,
                      int* nws, int B, int N, int L, float thresh, int cap, void* stream);
 
-/* ---- LVIS Fixed AP (csrc/lvis_eval.hip, host side mq_det_amd/evaluation.py LvisFixedAPEvaluator).  fp64 / fp32 / integer data only.
+/* ---- LVIS Fixed AP (csrc/ap_eval.hip: ap_match_kernel<LvisRules>, ap_accumulate_kernel<1>; host side mq_det_amd/evaluation.py LvisFixedAPEvaluator).  fp64 / fp32 / integer data only.
  * mq_lvis_match: LVISEval.evaluate_img for P (image, category) pairs.  pair_dt / pair_gt [P, 2] int32 = (first, count) of the pair's detections
  *   (sorted by score, dt_box [*, 4] fp32 xywh) and ground truths (annotation-file order: gt_box [*, 4] fp64 xywh, gt_area fp64, gt_ign uint8 =
  *   `ignore`, gt_nz uint8 = id != 0); pair_nel [P] uint8 = category in the image's not_exhaustive_category_ids; area_rng [4, 2] and iou_thr [10]
@@ -536,7 +536,7 @@ int mq_lvis_match(const int* pair_dt, const int* pair_gt, const unsigned char* p
 int mq_lvis_accumulate(const int* cat_off, const int* order, const unsigned long long* dt_bits, const int* num_gt, const double* rec_thr,
                        double* precision, double* recall, int K, void* stream);
 
-/* ---- COCO-style AP (csrc/coco_eval.hip, host side mq_det_amd/evaluation.py CocoAPEvaluator).  fp64 / fp32 / integer data only.
+/* ---- COCO-style AP (csrc/ap_eval.hip: the same two kernels as ap_match_kernel<CocoRules>, ap_accumulate_kernel<3>; host side mq_det_amd/evaluation.py CocoAPEvaluator).  fp64 / fp32 / integer data only.
  * mq_coco_match: pycocotools' COCOeval.evaluateImg for P (image, category) pairs.  pair_dt / pair_gt [P, 2] int32 = (first, count) of the pair's
  *   detections (sorted by score, already cut to maxDets[-1] = 100; dt_box [*, 4] fp32 xywh) and ground truths (annotation-file order: gt_box [*, 4]
  *   fp64 xywh, gt_area fp64 = the annotation's `area`, gt_crowd uint8 = iscrowd, gt_nz uint8 = id != 0); area_rng [4, 2] and iou_thr [10] fp64.

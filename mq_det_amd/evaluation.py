@@ -15,8 +15,8 @@ exchanges them between ranks by pickling the whole dict through two all_gathers 
   * `by_cat`      the reference's `{category: [ {"image_id", "category_id", "bbox", "score"} ]}` view for the LVIS API.
 Image ids must be exactly representable in fp32 (< 2^24; LVIS / COCO ids are < 600 000).
 
-`LvisFixedAPEvaluator` computes the LVIS Fixed AP from that state on the device (csrc/lvis_eval.hip; DESIGN.md "LVIS Fixed AP").
-`CocoAPEvaluator` computes pycocotools' COCO AP (COCO / ODinW) from rows of the same kind (csrc/coco_eval.hip; DESIGN.md "COCO AP").
+`LvisFixedAPEvaluator` computes the LVIS Fixed AP from that state on the device (csrc/ap_eval.hip; DESIGN.md "LVIS Fixed AP").
+`CocoAPEvaluator` computes pycocotools' COCO AP (COCO / ODinW) from rows of the same kind (csrc/ap_eval.hip, the same kernels under COCO's rules; DESIGN.md "COCO AP").
 `FlickrRecallEvaluator` computes Flickr30k Entities Recall@k (phrase grounding) from such rows (csrc/flickr_eval.hip; DESIGN.md "Phrase grounding").
 `update_packed` of the first two takes a forward's packed detections as they lie on the device: csrc/eval_rows.hip builds the rows in one launch and
 `append_block` keeps them with their device count until the next fold (mq_det_amd/detection.py; DESIGN.md "Detection evaluation loop")."""
@@ -171,58 +171,51 @@ def _ids(values, field):
     return a.astype(np.int64)
 
 
-class LvisFixedAPEvaluator:
-    """Drop-in for the reference's `LvisEvaluatorFixedAP` (data/datasets/evaluation/lvis/lvis_eval.py:766-875) on the default
-    `DATASETS.LVIS_USE_NORMAL_AP = False` path of engine/inference.py `build_lvis_evaluator`: the per-category top-k rows stay in a
-    `FixedAPAccumulator`, and `summarize()` runs `_summarize_fixed` (LVISResults(max_dets=-1) + LVISEval(iou_type="bbox"), params.max_dets = -1)
-    on the device: grouping with torch sorts, matching and accumulation in csrc/lvis_eval.hip, the summary means in torch; one host sync.
+def _not_main_process():
+    return dist.is_available() and dist.is_initialized() and dist.get_rank() != 0
 
-    gt: the reference's LVIS object (only `.dataset` is read), a dict in LVIS json format, or a path to such a json."""
 
-    def __init__(self, gt, topk=10000, device="cuda"):
+def _masked_mean(s):
+    """Mean of the entries above -1 (the kernels' mark for "no ground truth"), -1 where there is none; on the device."""
+    v = s > -1
+    n = v.sum()
+    return torch.where(n > 0, torch.where(v, s, torch.zeros((), dtype=s.dtype, device=s.device)).sum() / n.clamp(min=1),
+                       torch.full((), -1.0, dtype=torch.float64, device=s.device))
+
+
+class _APEvaluator:
+    """What LvisFixedAPEvaluator and CocoAPEvaluator share: the ground truth as device tensors, the (image, category) pairs the match
+    kernel of csrc/ap_eval.hip works on and the per-category order its accumulate kernel reads."""
+
+    def __init__(self, gt, device, acc):
+        """gt: path / dict / object with `.dataset`.  Indexes the images and categories; the class goes on with its own ingestion and ends
+        with `_ingest_annotations`."""
         if isinstance(gt, (str, os.PathLike)):
             with open(gt) as f:
                 gt = json.load(f)
-        ds = gt if isinstance(gt, dict) else gt.dataset
+        self._ds = gt if isinstance(gt, dict) else gt.dataset
         self.device = torch.device(device)
-        self.topk = int(topk)
-        self.acc = FixedAPAccumulator(self.topk, self.device)
+        self.acc = acc
         self._tie_overflow = None
         self.results = OrderedDict()
         self.eval = {}
         self.iou_thrs = np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1, endpoint=True)
         self.rec_thrs = np.linspace(0.0, 1.00, int(np.round((1.00 - 0.0) / 0.01)) + 1, endpoint=True)
-        self._ingest(ds)
+        self._imgs, self._cats = {}, {}
+        for img in self._ds["images"]:                 # LVIS._create_index / COCO.createIndex: the last image of an id wins
+            self._imgs[img["id"]] = img
+        for c in self._ds["categories"]:
+            self._cats[c["id"]] = c
+        self._img_ids = _ids(sorted(self._imgs), "images.id")
+        self._cat_ids = _ids(sorted(self._cats), "categories.id")
+        self.K = len(self._cat_ids)
+        self._img_pos = {int(i): n for n, i in enumerate(self._img_ids)}
+        self._cat_pos = {int(c): n for n, c in enumerate(self._cat_ids)}
 
-    # ------------------------------------------------------------------ ground truth, once
-    def _ingest(self, ds):
-        dev = self.device
-        imgs = {}
-        for img in ds["images"]:                       # LVIS._create_index: the last image of an id wins
-            imgs[img["id"]] = img
-        cats = {}
-        for c in ds["categories"]:
-            cats[c["id"]] = c
-        img_ids = _ids(sorted(imgs), "images.id")
-        cat_ids = _ids(sorted(cats), "categories.id")
-        K = len(cat_ids)
-        self.K = K
-        img_pos = {int(i): n for n, i in enumerate(img_ids)}
-        cat_pos = {int(c): n for n, c in enumerate(cat_ids)}
-        self.freq_groups = [[] for _ in _FREQ_LBL]
-        for n, c in enumerate(cat_ids):
-            self.freq_groups[_FREQ_LBL.index(cats[int(c)]["frequency"])].append(n)
-
-        def pair_keys(field):
-            keys = []
-            for i in img_ids:
-                lst = imgs[int(i)].get(field, [])
-                cs = _ids(lst, f"images.{field}")
-                keys.extend(img_pos[int(i)] * K + cat_pos[int(c)] for c in cs if int(c) in cat_pos)
-            return torch.tensor(sorted(set(keys)), dtype=torch.int64).to(dev)
-        self.neg_keys, self.nel_keys = pair_keys("neg_category_ids"), pair_keys("not_exhaustive_category_ids")
-
-        anns = ds["annotations"]
+    def _ingest_annotations(self, anns, ign_field, keep=None):
+        """anns: the file's annotation list; ign_field: the annotation field behind the kernel's per-ground-truth byte; keep(area): a further
+        filter.  Sets the ground-truth tensors and the kernels' tables; -> the byte on the device."""
+        dev, K, img_pos, cat_pos = self.device, self.K, self._img_pos, self._cat_pos
         a_img = _ids([a["image_id"] for a in anns], "annotations.image_id")
         a_cat = _ids([a["category_id"] for a in anns], "annotations.category_id")
         a_id = np.asarray([a["id"] for a in anns], dtype=np.int64).reshape(-1)
@@ -230,11 +223,12 @@ class LvisFixedAPEvaluator:
             raise ValueError("annotations.id: ids must be unique")
         a_area = np.asarray([a["area"] for a in anns], dtype=np.float64).reshape(-1)
         a_box = np.asarray([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
-        a_ign = np.asarray([bool(a.get("ignore", 0)) for a in anns], dtype=np.uint8).reshape(-1)
-        # get_ann_ids(img_ids, cat_ids): images of the file, categories of the file, 0 < area < inf
-        keep = np.array([int(i) in img_pos and int(c) in cat_pos for i, c in zip(a_img, a_cat)], dtype=bool).reshape(-1)
-        keep &= (a_area > 0) & (a_area < np.inf)
-        idx = np.nonzero(keep)[0]
+        a_ign = np.asarray([bool(a.get(ign_field, 0)) for a in anns], dtype=np.uint8).reshape(-1)
+        # get_ann_ids / getAnnIds(img_ids, cat_ids): images of the file, categories of the file
+        ok = np.array([int(i) in img_pos and int(c) in cat_pos for i, c in zip(a_img, a_cat)], dtype=bool).reshape(-1)
+        if keep is not None:
+            ok &= keep(a_area)
+        idx = np.nonzero(ok)[0]
         key = np.array([img_pos[int(a_img[j])] * K + cat_pos[int(a_cat[j])] for j in idx], dtype=np.int64)
         o = np.argsort(key, kind="stable")                  # per pair in annotation-file order
         idx, key = idx[o], key[o]
@@ -242,14 +236,70 @@ class LvisFixedAPEvaluator:
         self.gt_key = t(key, torch.int64)
         self.gt_box = t(a_box[idx].reshape(-1, 4), torch.float64)
         self.gt_area = t(a_area[idx], torch.float64)
-        self.gt_ign = t(a_ign[idx], torch.uint8)
         self.gt_nz = t(a_id[idx] != 0, torch.uint8)
-        self.img_ids_f = t(img_ids.astype(np.float64), torch.float64)
-        self.cat_ids_f = t(cat_ids.astype(np.float64), torch.float64)
+        self.img_ids_f = t(self._img_ids.astype(np.float64), torch.float64)
+        self.cat_ids_f = t(self._cat_ids.astype(np.float64), torch.float64)
         self.area_rng_t = t(np.asarray(_AREA_RNG, np.float64), torch.float64)
         self.iou_thr_t = t(self.iou_thrs, torch.float64)
         self.rec_thr_t = t(self.rec_thrs, torch.float64)
-        self.freq_t = [t(np.asarray(g, np.int64), torch.int64) for g in self.freq_groups]
+        del self._ds                                        # only held between the two steps of the constructor
+        return t(a_ign[idx], torch.uint8)
+
+    def tie_overflow(self):
+        """Whether a forward that came through `update_packed` had more detections tied with the DETECTIONS_PER_IMG-th score than tie slots
+        (`last_tie_overflow` of the BoxList path).  One host sync."""
+        return self._tie_overflow is not None and bool(self._tie_overflow.item())
+
+    def _pairs(self, dkey):
+        """Sorted pair keys of the kept detections -> (pkey: every (image, category) pair with a gt or a detection, pair_dt, pair_gt
+        [P, 2] int32 = (first, count) of the pair's detections / ground truths)."""
+        pkey = torch.unique(torch.cat([self.gt_key, dkey]))
+        ds, de = torch.searchsorted(dkey, pkey), torch.searchsorted(dkey, pkey, right=True)
+        gs, ge = torch.searchsorted(self.gt_key, pkey), torch.searchsorted(self.gt_key, pkey, right=True)
+        return pkey, torch.stack([ds, de - ds], 1).to(torch.int32).contiguous(), torch.stack([gs, ge - gs], 1).to(torch.int32).contiguous()
+
+    def _by_category(self, rows, dkey, pkey, gt_count):
+        """After the match -> (num_gt [K, 4] int64, accumulate's order per category: score descending, ties by image id, then by the
+        position in the pair, int32; cat_off [K + 1] int32)."""
+        K, dev = self.K, self.device
+        num_gt = torch.zeros(K, 4, dtype=torch.int64, device=dev)
+        if K:
+            num_gt.index_add_(0, pkey % K, gt_count.long())
+        dcat = dkey % K if K else dkey
+        o = torch.sort(rows[:, 2], descending=True, stable=True)[1]
+        o = o[torch.sort(dcat[o], stable=True)[1]]
+        cat_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        cat_off[1:] = torch.cumsum(torch.bincount(dcat, minlength=K)[:K], 0)
+        return num_gt, o.to(torch.int32), cat_off.to(torch.int32)
+
+
+class LvisFixedAPEvaluator(_APEvaluator):
+    """Drop-in for the reference's `LvisEvaluatorFixedAP` (data/datasets/evaluation/lvis/lvis_eval.py:766-875) on the default
+    `DATASETS.LVIS_USE_NORMAL_AP = False` path of engine/inference.py `build_lvis_evaluator`: the per-category top-k rows stay in a
+    `FixedAPAccumulator`, and `summarize()` runs `_summarize_fixed` (LVISResults(max_dets=-1) + LVISEval(iou_type="bbox"), params.max_dets = -1)
+    on the device: grouping with torch sorts, matching and accumulation in csrc/ap_eval.hip, the summary means in torch; one host sync.
+
+    gt: the reference's LVIS object (only `.dataset` is read), a dict in LVIS json format, or a path to such a json."""
+
+    def __init__(self, gt, topk=10000, device="cuda"):
+        self.topk = int(topk)
+        super().__init__(gt, device, FixedAPAccumulator(self.topk, device))
+        dev, K = self.device, self.K
+        self.freq_groups = [[] for _ in _FREQ_LBL]
+        for n, c in enumerate(self._cat_ids):
+            self.freq_groups[_FREQ_LBL.index(self._cats[int(c)]["frequency"])].append(n)
+        self.freq_t = [torch.tensor(g, dtype=torch.int64).to(dev) for g in self.freq_groups]
+
+        def pair_keys(field):
+            keys = []
+            for i in self._img_ids:
+                lst = self._imgs[int(i)].get(field, [])
+                cs = _ids(lst, f"images.{field}")
+                keys.extend(self._img_pos[int(i)] * K + self._cat_pos[int(c)] for c in cs if int(c) in self._cat_pos)
+            return torch.tensor(sorted(set(keys)), dtype=torch.int64).to(dev)
+        self.neg_keys, self.nel_keys = pair_keys("neg_category_ids"), pair_keys("not_exhaustive_category_ids")
+        # get_ann_ids: 0 < area < inf
+        self.gt_ign = self._ingest_annotations(self._ds["annotations"], "ignore", keep=lambda area: (area > 0) & (area < np.inf))
 
     # ------------------------------------------------------------------ the engine's calls
     def update(self, predictions):
@@ -277,11 +327,6 @@ class LvisFixedAPEvaluator:
                                    ratios=[(float(ow) / float(iw), float(oh) / float(ih)) for (ih, iw), (oh, ow) in zip(input_sizes, orig_sizes)])
         self.acc.append_block(rows, state[0])
 
-    def tie_overflow(self):
-        """Whether a forward that came through `update_packed` had more detections tied with the DETECTIONS_PER_IMG-th score than tie slots
-        (`last_tie_overflow` of the BoxList path).  One host sync."""
-        return self._tie_overflow is not None and bool(self._tie_overflow.item())
-
     def synchronize_between_processes(self):
         self.acc.synchronize_between_processes()
 
@@ -306,7 +351,7 @@ class LvisFixedAPEvaluator:
 
     def summarize(self):
         """Main process: the strings of LVISEval.print_results (max_dets = -1) and self.results; other ranks: None."""
-        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+        if _not_main_process():
             return None
         precision, recall = self.evaluate()
         vals = []
@@ -349,26 +394,14 @@ class LvisFixedAPEvaluator:
         """-> (precision [10, 101, K, 4], recall [10, K, 4]) fp64 on the device, as LVISEval.accumulate lays them out; also kept in self.eval
         with the per-detection match bits (test hooks)."""
         from . import ops
-        K, dev = self.K, self.device
         rows, dkey = self._rows()
-        pkey = torch.unique(torch.cat([self.gt_key, dkey]))                       # every (image, category) pair with a gt or a detection
-        i32 = lambda x: x.to(torch.int32)                                          # noqa: E731
-        ds, de = torch.searchsorted(dkey, pkey), torch.searchsorted(dkey, pkey, right=True)
-        gs, ge = torch.searchsorted(self.gt_key, pkey), torch.searchsorted(self.gt_key, pkey, right=True)
-        pair_dt = i32(torch.stack([ds, de - ds], 1)).contiguous()
-        pair_gt = i32(torch.stack([gs, ge - gs], 1)).contiguous()
+        pkey, pair_dt, pair_gt = self._pairs(dkey)
         pair_nel = self._member(self.nel_keys, pkey).to(torch.uint8)
         dt_box = rows[:, 3:7].contiguous()
         dt_bits, gt_count = ops.lvis_match(pair_dt, pair_gt, pair_nel, dt_box, self.gt_box, self.gt_area, self.gt_ign, self.gt_nz,
                                            self.area_rng_t, self.iou_thr_t)
-        num_gt = torch.zeros(K, 4, dtype=torch.int64, device=dev)
-        num_gt.index_add_(0, pkey % K, gt_count.long())
-        # accumulate's order per category: score descending, ties by image id, then by the position in the pair
-        o = torch.sort(rows[:, 2], descending=True, stable=True)[1]
-        o = o[torch.sort((dkey % K)[o], stable=True)[1]]
-        cat_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        cat_off[1:] = torch.cumsum(torch.bincount(dkey % K, minlength=K), 0)
-        precision, recall = ops.lvis_accumulate(i32(cat_off), i32(o), dt_bits, i32(num_gt).contiguous(), self.rec_thr_t)
+        num_gt, order, cat_off = self._by_category(rows, dkey, pkey, gt_count)
+        precision, recall = ops.lvis_accumulate(cat_off, order, dt_bits, num_gt.to(torch.int32).contiguous(), self.rec_thr_t)
         self.eval = {"precision": precision, "recall": recall, "pair_key": pkey, "pair_dt": pair_dt, "pair_gt": pair_gt,
                      "dt_bits": dt_bits, "gt_count": gt_count, "num_gt": num_gt}
         return precision, recall
@@ -395,10 +428,7 @@ class LvisFixedAPEvaluator:
             s = s[..., aidx]
         else:
             s = s[:, :, aidx]
-        v = s > -1
-        n = v.sum()
-        return torch.where(n > 0, torch.where(v, s, torch.zeros((), dtype=s.dtype, device=s.device)).sum() / n.clamp(min=1),
-                           torch.full((), -1.0, dtype=torch.float64, device=s.device))
+        return _masked_mean(s)
 
     def print_results(self):
         template = " {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} catIds={:>3s}] = {:0.3f}"
@@ -443,80 +473,29 @@ class _ResultRows(FixedAPAccumulator):
         return rows
 
 
-class CocoAPEvaluator:
+class CocoAPEvaluator(_APEvaluator):
     """The COCO / ODinW branch of the reference's engine/inference.py (:649-650 `results_dict.update`, :703-708 the gather, :749-763 `evaluate` ->
     data/datasets/evaluation/coco/coco_eval.py `do_coco_evaluation`: `prepare_for_coco_detection`, pycocotools `COCOeval` for iou_type bbox,
     `summarize_per_category`, `COCOResults`) with the detections kept as device rows: `update` resizes, converts and maps labels on the device,
     `synchronize_between_processes` is `FixedAPAccumulator`'s fixed-shape exchange, `summarize()` groups with torch sorts, matches and
-    accumulates in csrc/coco_eval.hip and takes the twelve means in torch; one host sync.
+    accumulates in csrc/ap_eval.hip and takes the twelve means in torch; one host sync.
 
     gt: the reference's `dataset.coco` (only `.dataset` is read), a dict in COCO json format, or a path to such a json.
     label_to_cat_id: the dataset's `contiguous_category_id_to_json_id`; default {i + 1: id} over the sorted category ids."""
 
     def __init__(self, gt, device="cuda", label_to_cat_id=None):
-        if isinstance(gt, (str, os.PathLike)):
-            with open(gt) as f:
-                gt = json.load(f)
-        ds = gt if isinstance(gt, dict) else gt.dataset
-        self.device = torch.device(device)
-        self.acc = _ResultRows(self.device)
-        self._tie_overflow = None
-        self.results = OrderedDict()
+        super().__init__(gt, device, _ResultRows(device))
         self.stats = []
-        self.eval = {}
-        self.iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
-        self.rec_thrs = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
-        self._ingest(ds)
+        self.cat_ids = [int(c) for c in self._cat_ids]           # params.catIds
+        self.cat_names = [self._cats[c].get("name", str(c)) for c in sorted(self._cats)]
+        self.img_size = {int(i): (img["width"], img["height"]) for i, img in sorted(self._imgs.items()) if "width" in img and "height" in img}
+        self.gt_crowd = self._ingest_annotations(self._ds.get("annotations", []), "iscrowd")
         if label_to_cat_id is None:
             label_to_cat_id = {i + 1: c for i, c in enumerate(self.cat_ids)}
         labels = sorted(label_to_cat_id)
         self.lbl_keys = torch.from_numpy(_ids(labels, "label_to_cat_id")).to(self.device)
         self.lbl_vals = torch.from_numpy(_ids([label_to_cat_id[k] for k in labels], "label_to_cat_id")).float().to(self.device)
         self.lbl_keys32 = self.lbl_keys.to(torch.int32)          # (ids lie within +-2^24) the kernel's table
-
-    # ------------------------------------------------------------------ ground truth, once
-    def _ingest(self, ds):
-        dev = self.device
-        imgs = {}
-        for img in ds["images"]:                       # COCO.createIndex: the last image of an id wins
-            imgs[img["id"]] = img
-        cats = {}
-        for c in ds["categories"]:
-            cats[c["id"]] = c
-        img_ids = _ids(sorted(imgs), "images.id")      # params.imgIds / catIds
-        cat_ids = _ids(sorted(cats), "categories.id")
-        K = len(cat_ids)
-        self.K = K
-        self.cat_ids = [int(c) for c in cat_ids]
-        self.cat_names = [cats[c].get("name", str(c)) for c in sorted(cats)]
-        self.img_size = {int(i): (imgs[i]["width"], imgs[i]["height"]) for i in sorted(imgs) if "width" in imgs[i] and "height" in imgs[i]}
-        img_pos = {int(i): n for n, i in enumerate(img_ids)}
-        cat_pos = {int(c): n for n, c in enumerate(cat_ids)}
-        anns = ds.get("annotations", [])
-        a_img = _ids([a["image_id"] for a in anns], "annotations.image_id")
-        a_cat = _ids([a["category_id"] for a in anns], "annotations.category_id")
-        a_id = np.asarray([a["id"] for a in anns], dtype=np.int64).reshape(-1)
-        if len(np.unique(a_id)) != len(a_id):
-            raise ValueError("annotations.id: ids must be unique")
-        a_area = np.asarray([a["area"] for a in anns], dtype=np.float64).reshape(-1)
-        a_box = np.asarray([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
-        a_crowd = np.asarray([bool(a.get("iscrowd", 0)) for a in anns], dtype=np.uint8).reshape(-1)
-        # getAnnIds(imgIds, catIds): images of the file, categories of the file
-        idx = np.nonzero(np.array([int(i) in img_pos and int(c) in cat_pos for i, c in zip(a_img, a_cat)], dtype=bool).reshape(-1))[0]
-        key = np.array([img_pos[int(a_img[j])] * K + cat_pos[int(a_cat[j])] for j in idx], dtype=np.int64)
-        o = np.argsort(key, kind="stable")                  # per pair in annotation-file order
-        idx, key = idx[o], key[o]
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev)       # noqa: E731
-        self.gt_key = t(key, torch.int64)
-        self.gt_box = t(a_box[idx].reshape(-1, 4), torch.float64)
-        self.gt_area = t(a_area[idx], torch.float64)
-        self.gt_crowd = t(a_crowd[idx], torch.uint8)
-        self.gt_nz = t(a_id[idx] != 0, torch.uint8)
-        self.img_ids_f = t(img_ids.astype(np.float64), torch.float64)
-        self.cat_ids_f = t(cat_ids.astype(np.float64), torch.float64)
-        self.area_rng_t = t(np.asarray(_AREA_RNG, np.float64), torch.float64)
-        self.iou_thr_t = t(self.iou_thrs, torch.float64)
-        self.rec_thr_t = t(self.rec_thrs, torch.float64)
 
     # ------------------------------------------------------------------ the engine's calls
     def update(self, predictions):
@@ -565,8 +544,6 @@ class CocoAPEvaluator:
                                    lbl_keys=self.lbl_keys32, lbl_vals=self.lbl_vals)
         self.acc.append_block(rows, state[0])
 
-    tie_overflow = LvisFixedAPEvaluator.tie_overflow
-
     def synchronize_between_processes(self, group=None, force=False):
         self.acc.synchronize_between_processes(group, force)
 
@@ -613,27 +590,14 @@ class CocoAPEvaluator:
         """-> (precision [10, 101, K, 4, 3], recall [10, K, 4, 3]) fp64 on the device, as COCOeval.accumulate lays them out; also kept in
         self.eval with the per-detection match bits (test hooks)."""
         from . import ops
-        K, dev = self.K, self.device
         rows, dkey, rank, unknown = self._rows()
-        pkey = torch.unique(torch.cat([self.gt_key, dkey]))                       # every (image, category) pair with a gt or a detection
-        i32 = lambda x: x.to(torch.int32)                                          # noqa: E731
-        ds, de = torch.searchsorted(dkey, pkey), torch.searchsorted(dkey, pkey, right=True)
-        gs, ge = torch.searchsorted(self.gt_key, pkey), torch.searchsorted(self.gt_key, pkey, right=True)
-        pair_dt = i32(torch.stack([ds, de - ds], 1)).contiguous()
-        pair_gt = i32(torch.stack([gs, ge - gs], 1)).contiguous()
+        pkey, pair_dt, pair_gt = self._pairs(dkey)
         dt_box = rows[:, 3:7].contiguous()
         dt_bits, gt_count = ops.coco_match(pair_dt, pair_gt, dt_box, self.gt_box, self.gt_area, self.gt_crowd, self.gt_nz, self.area_rng_t,
                                            self.iou_thr_t)
-        num_gt = torch.zeros(K, 4, dtype=torch.int64, device=dev)
-        if K:
-            num_gt.index_add_(0, pkey % K, gt_count.long())
-        # accumulate's order per category: score descending, ties by image id, then by the rank in the pair
-        dcat = dkey % K if K else dkey
-        o = torch.sort(rows[:, 2], descending=True, stable=True)[1]
-        o = o[torch.sort(dcat[o], stable=True)[1]]
-        cat_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        cat_off[1:] = torch.cumsum(torch.bincount(dcat, minlength=K)[:K], 0)
-        precision, recall = ops.coco_accumulate(i32(cat_off), i32(o), i32(rank).contiguous(), dt_bits, i32(num_gt).contiguous(), self.rec_thr_t)
+        num_gt, order, cat_off = self._by_category(rows, dkey, pkey, gt_count)
+        precision, recall = ops.coco_accumulate(cat_off, order, rank.to(torch.int32).contiguous(), dt_bits, num_gt.to(torch.int32).contiguous(),
+                                                self.rec_thr_t)
         self.eval = {"precision": precision, "recall": recall, "pair_key": pkey, "pair_dt": pair_dt, "pair_gt": pair_gt, "dt_bits": dt_bits,
                      "gt_count": gt_count, "num_gt": num_gt, "rows": rows, "rank": rank, "unknown_images": unknown}
         return precision, recall
@@ -643,14 +607,11 @@ class CocoAPEvaluator:
         if iou_thr is not None:
             s = s[torch.as_tensor(np.where(iou_thr == self.iou_thrs)[0], device=s.device)]
         s = s[..., _AREA_LBL.index(area), _COCO_MAX_DETS.index(max_det)]
-        v = s > -1
-        n = v.sum()
-        return torch.where(n > 0, torch.where(v, s, torch.zeros((), dtype=s.dtype, device=s.device)).sum() / n.clamp(min=1),
-                           torch.full((), -1.0, dtype=torch.float64, device=s.device))
+        return _masked_mean(s)
 
     def summarize(self):
         """Main process: the twelve lines COCOeval.summarize prints, self.stats and self.results["bbox"]; other ranks: None."""
-        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+        if _not_main_process():
             return None
         precision, recall = self.evaluate()
         vals = [self._mean(precision if ap else recall, thr, area, md) for ap, thr, area, md in _COCO_SPECS]
@@ -672,7 +633,7 @@ class CocoAPEvaluator:
         """Main process: the lines of the reference's `summarize_per_category` (title, then AP / AP50 / APs / APm / APl at maxDets 100: the
         per-category `np.mean` over thresholds and recall points, -1 entries included), also written to `csv_output` when given; other
         ranks: None.  Not a hot path: the precision array comes to the host and numpy takes the means, so that the digits are numpy's."""
-        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+        if _not_main_process():
             return None
         if "precision" not in self.eval:
             self.evaluate()

@@ -1746,87 +1746,84 @@ def _tta_merge_special(lib, boxes_s, scores_s, labels_s, src_s, nvalid, cls_rank
     return boxes_o, scores_o, labels_o, n_out, ndrop
 
 
-# ---- LVIS Fixed AP (csrc/lvis_eval.hip; host side: mq_det_amd/evaluation.py LvisFixedAPEvaluator)
-LVIS_MATCH_LANES = 40                         # (area range, IoU threshold) scans per pair: the rows of the slow path's workspace
+# ---- LVIS Fixed AP and COCO-style AP (csrc/ap_eval.hip; host side: mq_det_amd/evaluation.py LvisFixedAPEvaluator / CocoAPEvaluator)
+AP_MATCH_LANES = 40                           # (area range, IoU threshold) scans per pair: the rows of the slow path's workspace
+COCO_MAX_DETS = (1, 10, 100)
+
+
+def _ap_match(fn, tag, pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz, area_rng, iou_thr):
+    """The match launch of both evaluators; fn: the library's entry point, tag: its timing tag.  pair_nel: LVIS's not-exhaustive byte per
+    pair; None under COCO, whose entry point has no such argument."""
+    _need_gpu(pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_ign, gt_nz, area_rng, iou_thr)
+    assert pair_dt.dtype == pair_gt.dtype == torch.int32 and gt_ign.dtype == gt_nz.dtype == torch.uint8
+    assert dt_box.dtype == torch.float32 and gt_box.dtype == gt_area.dtype == area_rng.dtype == iou_thr.dtype == torch.float64
+    assert area_rng.numel() == 8 and iou_thr.numel() == 10
+    for t in (pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_ign, gt_nz):
+        assert t.is_contiguous()
+    P, Nd, Ng, dev = len(pair_dt), len(dt_box), len(gt_box), dt_box.device
+    assert len(pair_gt) == P and len(gt_area) == len(gt_ign) == len(gt_nz) == Ng
+    head = [_ptr(pair_dt), _ptr(pair_gt)]
+    if pair_nel is not None:
+        _need_gpu(pair_nel)
+        assert pair_nel.dtype == torch.uint8 and pair_nel.is_contiguous() and len(pair_nel) == P
+        head.append(_ptr(pair_nel))
+    dt_bits = torch.zeros(Nd, 2, dtype=torch.int64, device=dev)
+    gt_count = torch.zeros(P, 4, dtype=torch.int32, device=dev)
+    ws = torch.empty(AP_MATCH_LANES * max(Ng, 1), dtype=torch.uint8, device=dev)
+    with _timed(tag):
+        _chk(fn(*head, _ptr(dt_box), _ptr(gt_box), _ptr(gt_area), _ptr(gt_ign), _ptr(gt_nz), _ptr(area_rng), _ptr(iou_thr), _ptr(dt_bits),
+                _ptr(gt_count), _ptr(ws), P, Ng, _stream()), "mq_" + tag)
+    return dt_bits, gt_count
+
+
+def _ap_accumulate(fn, tag, cat_off, order, rank, dt_bits, num_gt, rec_thr):
+    """The accumulate launch of both evaluators.  rank: COCO's rank of every detection in its pair, which adds the maxDets axis
+    (COCO_MAX_DETS) to the outputs; None under LVIS, whose entry point takes neither rank nor maxDets."""
+    _need_gpu(cat_off, order, dt_bits, num_gt, rec_thr)
+    assert cat_off.dtype == order.dtype == num_gt.dtype == torch.int32 and dt_bits.dtype == torch.int64
+    assert rec_thr.dtype == torch.float64 and rec_thr.numel() == 101 and num_gt.is_contiguous() and dt_bits.is_contiguous()
+    assert len(order) <= len(dt_bits)
+    K, dev = len(cat_off) - 1, dt_bits.device
+    assert num_gt.numel() == 4 * K
+    if rank is None:
+        precision = torch.empty(10, 101, K, 4, dtype=torch.float64, device=dev)
+        recall = torch.empty(10, K, 4, dtype=torch.float64, device=dev)
+        args = [_ptr(cat_off), _ptr(order), _ptr(dt_bits), _ptr(num_gt)]
+    else:
+        _need_gpu(rank)
+        assert rank.dtype == torch.int32 and len(rank) == len(dt_bits)
+        max_dets = torch.tensor(COCO_MAX_DETS, dtype=torch.int32).to(dev)
+        precision = torch.empty(10, 101, K, 4, len(COCO_MAX_DETS), dtype=torch.float64, device=dev)
+        recall = torch.empty(10, K, 4, len(COCO_MAX_DETS), dtype=torch.float64, device=dev)
+        args = [_ptr(cat_off), _ptr(order), _ptr(rank), _ptr(dt_bits), _ptr(num_gt), _ptr(max_dets)]
+    with _timed(tag):
+        _chk(fn(*args, _ptr(rec_thr), _ptr(precision), _ptr(recall), K, _stream()), "mq_" + tag)
+    return precision, recall
 
 
 def lvis_match(pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz, area_rng, iou_thr):
     """evaluate_img for every pair -> (dt_bits [Nd, 2] int64 (uint64 bit patterns: matched, ignored; bit = area * 10 + threshold),
     gt_count [P, 4] int32 non-ignored ground truths per area range).  Layouts: include/mqdet_hip.h mq_lvis_match."""
-    lib = load_library()
-    _need_gpu(pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz, area_rng, iou_thr)
-    assert pair_dt.dtype == pair_gt.dtype == torch.int32 and pair_nel.dtype == gt_ign.dtype == gt_nz.dtype == torch.uint8
-    assert dt_box.dtype == torch.float32 and gt_box.dtype == gt_area.dtype == area_rng.dtype == iou_thr.dtype == torch.float64
-    assert area_rng.numel() == 8 and iou_thr.numel() == 10
-    for t in (pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz):
-        assert t.is_contiguous()
-    P, Nd, Ng, dev = len(pair_dt), len(dt_box), len(gt_box), dt_box.device
-    dt_bits = torch.zeros(Nd, 2, dtype=torch.int64, device=dev)
-    gt_count = torch.zeros(P, 4, dtype=torch.int32, device=dev)
-    ws = torch.empty(LVIS_MATCH_LANES * max(Ng, 1), dtype=torch.uint8, device=dev)
-    with _timed("lvis_match"):
-        _chk(lib.mq_lvis_match(_ptr(pair_dt), _ptr(pair_gt), _ptr(pair_nel), _ptr(dt_box), _ptr(gt_box), _ptr(gt_area), _ptr(gt_ign), _ptr(gt_nz),
-                               _ptr(area_rng), _ptr(iou_thr), _ptr(dt_bits), _ptr(gt_count), _ptr(ws), P, Ng, _stream()), "mq_lvis_match")
-    return dt_bits, gt_count
+    return _ap_match(load_library().mq_lvis_match, "lvis_match", pair_dt, pair_gt, pair_nel, dt_box, gt_box, gt_area, gt_ign, gt_nz, area_rng,
+                     iou_thr)
 
 
 def lvis_accumulate(cat_off, order, dt_bits, num_gt, rec_thr, n_thr=10):
     """accumulate -> (precision [10, 101, K, 4], recall [10, K, 4]) fp64.  Layouts: include/mqdet_hip.h mq_lvis_accumulate."""
-    lib = load_library()
-    _need_gpu(cat_off, order, dt_bits, num_gt, rec_thr)
-    assert cat_off.dtype == order.dtype == num_gt.dtype == torch.int32 and dt_bits.dtype == torch.int64 and rec_thr.dtype == torch.float64
-    assert rec_thr.numel() == 101 and n_thr == 10 and num_gt.is_contiguous() and dt_bits.is_contiguous()
-    K, dev = len(cat_off) - 1, dt_bits.device
-    precision = torch.empty(n_thr, 101, K, 4, dtype=torch.float64, device=dev)
-    recall = torch.empty(n_thr, K, 4, dtype=torch.float64, device=dev)
-    with _timed("lvis_accumulate"):
-        _chk(lib.mq_lvis_accumulate(_ptr(cat_off), _ptr(order), _ptr(dt_bits), _ptr(num_gt), _ptr(rec_thr), _ptr(precision), _ptr(recall), K,
-                                    _stream()), "mq_lvis_accumulate")
-    return precision, recall
-
-
-# ---- COCO-style AP (csrc/coco_eval.hip; host side: mq_det_amd/evaluation.py CocoAPEvaluator)
-COCO_MAX_DETS = (1, 10, 100)
+    assert n_thr == 10
+    return _ap_accumulate(load_library().mq_lvis_accumulate, "lvis_accumulate", cat_off, order, None, dt_bits, num_gt, rec_thr)
 
 
 def coco_match(pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_crowd, gt_nz, area_rng, iou_thr):
-    """evaluateImg for every pair -> (dt_bits [Nd, 2] int64 (uint64 bit patterns: matched, ignored; bit = area * 10 + threshold),
-    gt_count [P, 4] int32 non-ignored ground truths per area range).  Layouts: include/mqdet_hip.h mq_coco_match."""
-    lib = load_library()
-    _need_gpu(pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_crowd, gt_nz, area_rng, iou_thr)
-    assert pair_dt.dtype == pair_gt.dtype == torch.int32 and gt_crowd.dtype == gt_nz.dtype == torch.uint8
-    assert dt_box.dtype == torch.float32 and gt_box.dtype == gt_area.dtype == area_rng.dtype == iou_thr.dtype == torch.float64
-    assert area_rng.numel() == 8 and iou_thr.numel() == 10
-    for t in (pair_dt, pair_gt, dt_box, gt_box, gt_area, gt_crowd, gt_nz):
-        assert t.is_contiguous()
-    P, Nd, Ng, dev = len(pair_dt), len(dt_box), len(gt_box), dt_box.device
-    assert len(pair_gt) == P and len(gt_area) == len(gt_crowd) == len(gt_nz) == Ng
-    dt_bits = torch.zeros(Nd, 2, dtype=torch.int64, device=dev)
-    gt_count = torch.zeros(P, 4, dtype=torch.int32, device=dev)
-    ws = torch.empty(LVIS_MATCH_LANES * max(Ng, 1), dtype=torch.uint8, device=dev)
-    with _timed("coco_match"):
-        _chk(lib.mq_coco_match(_ptr(pair_dt), _ptr(pair_gt), _ptr(dt_box), _ptr(gt_box), _ptr(gt_area), _ptr(gt_crowd), _ptr(gt_nz),
-                               _ptr(area_rng), _ptr(iou_thr), _ptr(dt_bits), _ptr(gt_count), _ptr(ws), P, Ng, _stream()), "mq_coco_match")
-    return dt_bits, gt_count
+    """evaluateImg for every pair -> (dt_bits, gt_count) as lvis_match's.  Layouts: include/mqdet_hip.h mq_coco_match."""
+    return _ap_match(load_library().mq_coco_match, "coco_match", pair_dt, pair_gt, None, dt_box, gt_box, gt_area, gt_crowd, gt_nz, area_rng,
+                     iou_thr)
 
 
 def coco_accumulate(cat_off, order, rank, dt_bits, num_gt, rec_thr):
     """accumulate -> (precision [10, 101, K, 4, 3], recall [10, K, 4, 3]) fp64, maxDets = COCO_MAX_DETS.  Layouts: include/mqdet_hip.h
     mq_coco_accumulate."""
-    lib = load_library()
-    _need_gpu(cat_off, order, rank, dt_bits, num_gt, rec_thr)
-    assert cat_off.dtype == order.dtype == rank.dtype == num_gt.dtype == torch.int32 and dt_bits.dtype == torch.int64
-    assert rec_thr.dtype == torch.float64 and rec_thr.numel() == 101 and num_gt.is_contiguous() and dt_bits.is_contiguous()
-    assert len(rank) == len(dt_bits) and len(order) <= len(dt_bits)
-    K, dev = len(cat_off) - 1, dt_bits.device
-    assert num_gt.numel() == 4 * K
-    max_dets = torch.tensor(COCO_MAX_DETS, dtype=torch.int32).to(dev)
-    precision = torch.empty(10, 101, K, 4, 3, dtype=torch.float64, device=dev)
-    recall = torch.empty(10, K, 4, 3, dtype=torch.float64, device=dev)
-    with _timed("coco_accumulate"):
-        _chk(lib.mq_coco_accumulate(_ptr(cat_off), _ptr(order), _ptr(rank), _ptr(dt_bits), _ptr(num_gt), _ptr(max_dets), _ptr(rec_thr),
-                                    _ptr(precision), _ptr(recall), K, _stream()), "mq_coco_accumulate")
-    return precision, recall
+    return _ap_accumulate(load_library().mq_coco_accumulate, "coco_accumulate", cat_off, order, rank, dt_bits, num_gt, rec_thr)
 
 
 # ---- Flickr30k Entities Recall@k (csrc/flickr_eval.hip; host side: mq_det_amd/evaluation.py FlickrRecallEvaluator)

@@ -1,4 +1,4 @@
-"""COCO AP (mq_det_amd.evaluation.CocoAPEvaluator, csrc/coco_eval.hip) without a GPU: the kernel SOURCES through the host emulation (tests/simt)
+"""COCO AP (mq_det_amd.evaluation.CocoAPEvaluator, csrc/ap_eval.hip) without a GPU: the kernel SOURCES through the host emulation (tests/simt)
 against tests/golden/coco_eval_{bridge,small,medium} (tools/gen_golden_coco_eval.py).  `bridge` holds what the reference's own LVISEval gives
 on a ground truth where LVIS and COCO rules coincide -- that pins the restatement tests/coco_eval_ref.py, whose outputs are the expectation
 everywhere else (pycocotools is not installed where the fixtures are made; see that file's docstring).  One pair above the match kernel's
@@ -21,7 +21,7 @@ from mq_det_amd.structures import BoxList  # noqa: E402
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "coco_eval_")
 _CXX = os.environ.get("SIMT_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 needs_simt = pytest.mark.skipif(not os.path.exists(_CXX), reason=f"{_CXX} not found: the kernel-source emulation cannot be built here")
-FAST_GT = 256                                   # csrc/coco_eval.hip COCO_FAST_GT
+FAST_GT = 256                                   # csrc/ap_eval.hip CocoRules::fast_gt
 
 
 def load_case(name):

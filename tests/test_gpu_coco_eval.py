@@ -1,4 +1,4 @@
-"""COCO AP on the MI355X (mq_det_amd.evaluation.CocoAPEvaluator, csrc/coco_eval.hip): the three fixtures of tests/test_coco_eval_cpu.py and the
+"""COCO AP on the MI355X (mq_det_amd.evaluation.CocoAPEvaluator, csrc/ap_eval.hip): the three fixtures of tests/test_coco_eval_cpu.py and the
 pair above the fast path with the same exact comparisons, the same under the NaN poison halos of tests/halo.py, a 200-image x 20-category
 random case against the restatement, and the engine's calls (per-image concatenation of forward_chunks' detections, update, the RCCL exchange
 in a one-rank group, summarize) on detections of the tiny MQ-GLIP model.  No time is asserted (tools/coco_eval_bench.py measures)."""

@@ -1,4 +1,4 @@
-"""LVIS Fixed AP on the MI355X (mq_det_amd.evaluation.LvisFixedAPEvaluator, csrc/lvis_eval.hip): both reference fixtures bit for bit, the same
+"""LVIS Fixed AP on the MI355X (mq_det_amd.evaluation.LvisFixedAPEvaluator, csrc/ap_eval.hip): both reference fixtures bit for bit, the same
 under the NaN poison halos of tests/halo.py, one pair of more than 2 000 detections x 500 ground truths, the LVIS-minival shape (4 809 images,
 1 203 categories, 50 000 ground truths, topk 10 000 = 12M rows), and the engine's calls on detections of forward_chunks.  Every test runs its
 body in a process of its own under a time limit (a fault or a hang fails that test, not the session)."""

@@ -1,4 +1,4 @@
-"""LVIS Fixed AP (mq_det_amd.evaluation.LvisFixedAPEvaluator, csrc/lvis_eval.hip) without a GPU: the kernel SOURCES through the host emulation
+"""LVIS Fixed AP (mq_det_amd.evaluation.LvisFixedAPEvaluator, csrc/ap_eval.hip) without a GPU: the kernel SOURCES through the host emulation
 (tests/simt) against tests/golden/lvis_eval_{small,medium}, which tools/gen_golden_lvis_eval.py records by running the reference's lvis.py /
 lvis_eval.py in place (LvisEvaluatorFixedAP.update + _summarize_fixed); one pair of more than 2 000 detections and 500 ground truths (the
 kernel's slow path) against the restatement of evaluate_img in tests/lvis_eval_ref.py; the refusals of ids the fp32 rows cannot hold."""
@@ -17,6 +17,7 @@ import lvis_eval_ref as ref  # noqa: E402
 from mq_det_amd.evaluation import LvisFixedAPEvaluator  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lvis_eval_")
+FAST_GT = 512                                   # csrc/ap_eval.hip LvisRules::fast_gt
 _CXX = os.environ.get("SIMT_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 needs_simt = pytest.mark.skipif(not os.path.exists(_CXX), reason=f"{_CXX} not found: the kernel-source emulation cannot be built here")
 
@@ -174,7 +175,7 @@ def check_big_pair(device):
     ev.synchronize_between_processes()
     ev.summarize()
     pr = ev.acc.rows.cpu().numpy()
-    assert ev.eval["pair_gt"][0, 1].item() > 512 and ev.eval["pair_dt"][0, 1].item() > 2000
+    assert ev.eval["pair_gt"][0, 1].item() > FAST_GT and ev.eval["pair_dt"][0, 1].item() > 2000
     m, ig, cnt = pair_flags(ev)[(7, 3)]
     img_ids, cat_ids, gts, dts, nel, _ = ref.prepare(gt, pr, 10000)
     for ai, rng in enumerate(ref.AREA_RNG):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time CocoAPEvaluator.summarize() on the MI355X at a COCO val2017-like shape: 5 000 images, 80 categories, about 7 ground truths per
 image, 100 detections per image (mq_det_amd.utils.synth.synthetic_coco, seeded).  Reported: update() of all images, summarize() (grouping
-sorts + csrc/coco_eval.hip + the twelve means, ending in its one host sync) as the median and spread of `--runs` calls after one warm-up
+sorts + csrc/ap_eval.hip + the twelve means, ending in its one host sync) as the median and spread of `--runs` calls after one warm-up
 call, the two kernels' share from the HIP events of ops.start_timing(), and -- for scale -- the numpy restatement tests/coco_eval_ref.py
 on a tenth of the images (it is the test oracle, not a tuned evaluator).  One JSON line at the end.
 
