@@ -615,6 +615,41 @@ int mq_bank_select_add_fwd(const float* pool, const int* slots, const int* qsrc,
 int mq_eval_rows(const float* packed, const int* counts, const int* table, const int* table_host, const int* lbl_keys, const float* lbl_vals,
                  int n_lbl, float* rows, int* n_rows, int* overflow, int E, int items, int K2, int cols, long capacity, int flags, void* stream);
 
+/* ---- The ATSS training objective, forward only (csrc/atss_loss.hip, host side mq_det_amd/losses.py; rpn/loss.py:655-832, :850-1201 with
+ * USE_DOT_PRODUCT_TOKEN_LOSS and one anchor per location).  No entry point here uses floating-point atomics: every sum is per-lane, per-wave,
+ * per-workgroup partials and one fixed-order pass over them, so a result is the same bits from run to run.
+ *
+ * mq_atss_assign_fwd: anchors [A, 4] fp32 (the levels concatenated; the same for every image), lvl_off [NL + 1] HOST ints (anchor offsets of
+ * the levels, lvl_off[NL] = A, NL <= 8), gt [total_gt, 4] fp32 xyxy boxes of the batch packed image after image, gt_off [B + 1] int32 (device).
+ * Per gt and level the min(topk, anchors of the level) anchors with the smallest centre distance (a tie: the lower anchor index), their
+ * boxlist_iou (+1 convention) mean + UNBIASED std = the gt's threshold (one candidate in all: NaN, nothing passes).  An anchor is a positive
+ * candidate of a gt iff it is among those, IoU >= threshold and its centre lies inside the box by more than 0.01; the gt of the highest IoU
+ * wins, a tie goes to the lower gt.  -> matched [B, A] int32: the gt's index INSIDE its image, -1 background (an image without gts: all -1,
+ * where the reference's max over an empty dimension raises).  thr [total_gt] fp32 and kth [total_gt, NL] int64 are caller-allocated
+ * workspace (threshold, k-th key = squared-distance bits << 32 | anchor index).  topk <= 64.  -1: bad sizes. */
+int mq_atss_assign_fwd(const float* anchors, const int* lvl_off, const float* gt, const int* gt_off, float* thr, long long* kth, int* matched,
+                       int B, int A, int NL, int total_gt, int topk, void* stream);
+/* Per (image, anchor) from `matched`: cls_out [B, A] int64 = the matched gt's label (labels [total_gt] int64), 0 for background; reg_out [B, A, 4]
+ * fp32 = BoxCoder(10, 10, 5, 5).encode(matched gt, anchor), TO_REMOVE = 1 -- a background anchor carries the encoding of the image's FIRST gt
+ * (the reference's max over a row of -INF returns index 0), zeros in an image without gts.  Either output may be NULL.
+ * With reg [B, A, 4] / ctr [B, A] fp32 (the head's box deltas and centerness logits; both or neither), partials [B * ceil(A / 256), 5]
+ * workspace and sums [5]: over the anchors whose label is > 0
+ *   sums = (their number, S ct, S ct (1 - GIoU), S BCE-with-logits(ctr, ct), S (1 - GIoU)),
+ * ct = compute_centerness_targets, GIoU with the reference's max(x1, x2) fix-up of the predicted box and its two 1e-7 terms. */
+int mq_atss_box_loss_fwd(const float* anchors, const float* gt, const long long* labels, const int* gt_off, const int* matched,
+                         const float* reg, const float* ctr, long long* cls_out, float* reg_out, float* partials, float* sums, int B, int A,
+                         int total_gt, void* stream);
+/* The dot-product token loss (token_sigmoid_binary_focal_loss, summed) on the operands of mq_align_fused_fwd: tok [B, N, 256] and tk [B, T, 256]
+ * 16-bit (tk already divided by exp(log_scale)), tbias [B, T] fp32; logit = clamp(tok . tk + tbias, +-50000), formed by MFMA and never stored.
+ * matched [B, N] int32 as above; posmap [total_gt, Tpm] fp32, Tpm = the caption's FULL length (T <= Tpm after live-token compaction);
+ * text_mask [B, T] int32 (> 0: the column counts); kv_max as in mq_align_fused_fwd: columns >= 16 ceil(kv_max / 16) are never computed.
+ * Target of (b, a, t): posmap[gt_off[b] + matched[b, a], t] for a positive anchor; for a background anchor 1 at t = Tpm - 1 and 0 elsewhere
+ * (`unmatched_labels[-1] = 1`: it only counts under a caption of full length).  alpha < 0: no alpha_t factor.
+ * partials [B * ceil(N / 128)] workspace; -> loss [1] fp32.  Any T; -1: bad sizes. */
+int mq_token_focal_loss_fwd(const void* tok, const void* tk, const float* tbias, const int* matched, const float* posmap, const int* gt_off,
+                            const int* text_mask, float* partials, float* loss, int B, int N, int T, int kv_max, int Tpm, int total_gt,
+                            float alpha, float gamma, void* stream);
+
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --
  *     packed[((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8] = W[n][k]
@@ -707,6 +742,7 @@ MQ_BF16_TWIN(mq_box_decode)
 MQ_BF16_TWIN(mq_roi_align_fwd)
 MQ_BF16_TWIN(mq_msdeform_attn_fwd)
 MQ_BF16_TWIN(mq_msdeform_attn_q_fwd)
+MQ_BF16_TWIN(mq_token_focal_loss_fwd)
 
 /* ---- fp32 operands: the PRECISE mode (MODEL.COMPUTE_DTYPE = "float32"; BASELINE.json north_star: "outputs ... match the reference ...
  * within 1e-3").  `name_f32` is the SAME kernel source compiled a third time with every 16-bit operand a float (csrc/common.h under
@@ -771,6 +807,7 @@ MQ_F32_TWIN(mq_align_fused_fwd)
 MQ_F32_TWIN(mq_box_decode)
 MQ_F32_TWIN(mq_msdeform_attn_fwd)
 MQ_F32_TWIN(mq_msdeform_attn_q_fwd)
+MQ_F32_TWIN(mq_token_focal_loss_fwd)
 
 #ifdef __cplusplus
 }

@@ -111,7 +111,8 @@ def get_cfg():
                  ASPECT_RATIOS=(1.0,), SCALES_PER_OCTAVE=1, OCTAVE=2.0, STRADDLE_THRESH=0, FREEZE=False,
                  FORCE_BOXES=False, RETURN_FUSED_FEATURES=False),
         ATSS=dict(NUM_CLASSES=81, PRIOR_PROB=0.01, INFERENCE_TH=0.05, NMS_TH=0.6, PRE_NMS_TOP_N=1000,
-                  DETECTIONS_PER_IMG=100),                                                             # :407-436
+                  DETECTIONS_PER_IMG=100,                                                              # :407-436
+                  TOPK=9, REG_LOSS_WEIGHT=2.0),                # :422-425, read by mq_det_amd.losses (the forward-only training objective)
         RETINANET=dict(INFERENCE_TH=0.05),    # :347, read by the TTA merge's TEST.SPECIAL_NMS = 'soft-vote' (box_aug.py:326) only
         DYHEAD=dict(NUM_CLASSES=81, PRIOR_PROB=0.01, NUM_CONVS=6, CHANNELS=256, USE_GN=True, USE_DYRELU=True,
                     USE_DFCONV=True, USE_DYFUSE=True, FUSED_DCN=True, LEVEL_STREAMS=True, SCORE_AGG="MEAN", LOG_SCALE=0.0, USE_CHECKPOINT=False,
@@ -121,7 +122,11 @@ def get_cfg():
                                      CLAMP_BERTATTN_MIN_FOR_UNDERFLOW=True, CLAMP_BERTATTN_MAX_FOR_OVERFLOW=True,
                                      CLAMP_DOT_PRODUCT=True, SEPARATE_BIDIRECTIONAL=False, STABLE_SOFTMAX_2D=False,
                                      ADD_LINEAR_LAYER=False, MLM_LOSS=False, USE_TOKEN_LOSS=False,
-                                     USE_CONTRASTIVE_ALIGN_LOSS=False)),
+                                     USE_CONTRASTIVE_ALIGN_LOSS=False,
+                                     # the loss switches and weights mq_det_amd.losses reads (:480-523)
+                                     USE_CLASSIFICATION_LOSS=False, USE_SHALLOW_CONTRASTIVE_LOSS=False,
+                                     USE_BACKBONE_SHALLOW_CONTRASTIVE_LOSS=False, TOKEN_ALPHA=0.25, TOKEN_GAMMA=2.0,
+                                     DOT_PRODUCT_TOKEN_LOSS_WEIGHT=1.0)),
         ROI_BOX_HEAD=dict(POOLER_RESOLUTION=7, POOLER_SCALES=(0.125, 0.0625, 0.03125, 0.015625, 0.0078125),
                           POOLER_SAMPLING_RATIO=0),
     ))

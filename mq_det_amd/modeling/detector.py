@@ -279,9 +279,8 @@ class GeneralizedVLRCNN_New(DeviceModel):
         pooled = pipeline.pooled_fpn_tokens(feats) if self._use_vq() else None
         return feats, pooled
 
-    def _head_stage(self, feats, pooled, front, input_ids, attention_mask, vision, idx, tokidx, label_ids, im_wh, max_kv,
-                    want_raw=False):
-        """Image-dependent half of the language backbone (pre-select + GCP / BERT layers), VLDyHead, post-processing."""
+    def _head_operands(self, feats, pooled, front, input_ids, attention_mask, vision, idx, max_kv, want_raw=False):
+        """The head stage up to what `postprocess` (or `ATSSLoss`) is handed: (lang, head, trace)."""
         P, cfg = self._plan, self.cfg
         lang = pipeline.language_backbone(P, cfg, input_ids, attention_mask, vision, pooled, idx,
                                           want_gates=cfg.VISION_QUERY.RETURN_ATTN_GATE_VALUE, front=front, max_kv=max_kv,
@@ -291,6 +290,13 @@ class GeneralizedVLRCNN_New(DeviceModel):
         pipeline.prompt_offset(P, lang)                           # the tuned prompt of a fine-tuned checkpoint (ADD_LINEAR_LAYER); else nothing
         trace = [] if want_raw else None                          # raw mode: per-layer tensors, single-stream schedule
         head = pipeline.vldyhead(P, cfg, feats, lang, trace=trace)
+        return lang, head, trace
+
+    def _head_stage(self, feats, pooled, front, input_ids, attention_mask, vision, idx, tokidx, label_ids, im_wh, max_kv,
+                    want_raw=False):
+        """Image-dependent half of the language backbone (pre-select + GCP / BERT layers), VLDyHead, post-processing."""
+        cfg = self.cfg
+        lang, head, trace = self._head_operands(feats, pooled, front, input_ids, attention_mask, vision, idx, max_kv, want_raw=want_raw)
         anchors = self._anchors(feats)
         post = pipeline.postprocess(cfg, head, anchors, im_wh, tokidx, label_ids, want_cls=want_raw)
         if want_raw:
@@ -599,6 +605,80 @@ class GeneralizedVLRCNN_New(DeviceModel):
             counts = out["counts"].tolist()                       # the one device->host sync of the forward
         result = self._boxlists(packed, self._split_counts(counts), images.image_sizes)
         return (result, gates) if cfg.VISION_QUERY.RETURN_ATTN_GATE_VALUE else result
+
+    # ------------------------------------------------------------------ the training objective, forward only (mq_det_amd/losses.py)
+    @torch.no_grad()
+    def forward_losses(self, images, targets, captions=None, positive_map=None, input_ids=None, attention_mask=None):
+        """The ATSS objective of the reference's training forward (rpn/loss.py:850-1201 under the mq-glip-*.yaml loss switches) on the
+        DETERMINISTIC EVAL-MODE forward: no autograd, no dropout, `model.train()` keeps raising.  targets: one BoxList per image (xyxy,
+        field 'labels', input-image coordinates, any device); captions: one string per image (one string serves the batch);
+        positive_map [sum of gts, MAX_QUERY_LEN], default the concatenation of the targets' 'positive_map' fields as the reference's forward
+        builds it.  Runs the eval programs up to the head stage -- per-image vision queries, [MASK]ed ids of the vision-only mode, the
+        backbone cache, live-token compaction, as `forward_grounding` --, then `ATSSLoss` instead of `postprocess`.  The label -> token table
+        the vision-query selection needs is read ON THE HOST from the labels and positive-map rows: pass them as the loader yields them
+        (CPU tensors) and the call makes no device->host transfer.  Eager (no HIP graph).  With the fused head operands the token loss is
+        formed without writing logits; the GEMM-fallback head (captions over 256 tokens, other widths) has materialised them already and the
+        loss is evaluated on them by a plain torch path.  -> {'loss_reg', 'loss_centerness', 'loss_dot_product_token', 'loss_cls',
+        'sums' [6] (losses.SUM_NAMES), 'matched' [B, A]}, all on the device.  `input_ids` / `attention_mask` [B, T] (tests, as in `forward`):
+        caller-supplied token ids instead of captions, one host synchronisation for the key-length bound."""
+        if self.training:
+            raise NotImplementedError("training forward is out of scope")
+        from ..losses import ATSSLoss
+        criterion = ATSSLoss(self.cfg)                            # refuses unsupported loss settings by name, before anything is launched
+        images = to_image_list(images)
+        dev = images.tensors.device
+        P = self._ensure_plan(dev)
+        dtype = P["backbone.body.patch_embed.proj.weight"].dtype
+        Bn = images.tensors.shape[0]
+        if input_ids is None:
+            if captions is None:
+                raise ValueError("forward_losses: captions (or input_ids and attention_mask) are needed")
+            captions = [captions] * Bn if isinstance(captions, str) else list(captions)
+            if len(captions) == 1 and Bn > 1:
+                captions = captions * Bn
+            toks = [self.tokenize([cap], dev) for cap in captions]
+        else:
+            kv_all = int((attention_mask.cpu() * torch.arange(1, attention_mask.shape[1] + 1)).max())
+            toks = [(input_ids[b:b + 1].to(dev), attention_mask[b:b + 1].to(dev), kv_all) for b in range(len(input_ids))]
+            captions = [None] * len(toks)
+        if len(targets) != Bn or len(toks) != Bn:
+            raise ValueError(f"forward_losses: {Bn} images, {len(targets)} targets, {len(toks)} captions")
+        if positive_map is None:
+            if not all("positive_map" in t.fields() for t in targets):
+                raise ValueError("forward_losses: no positive_map given and the targets carry no 'positive_map' field")
+            positive_map = torch.cat([t.get_field("positive_map") for t in targets], 0)
+        ids, ams, kvs, pms, labs = [], [], [], [], []
+        off = 0
+        for cap, (i, a, kv), t in zip(captions, toks, targets):
+            n = len(t.bbox)
+            rows, lab_t = positive_map[off:off + n], t.get_field("labels")
+            off += n
+            table = {}
+            if self._use_vq():                                    # {label: token positions} of this image, for the vision queries / [MASK]ing
+                lab_l = lab_t.tolist()
+                for r_, c_ in (rows > 0).nonzero().tolist():
+                    table.setdefault(int(lab_l[r_]), set()).add(c_)
+            pm, lab, pm_key, _, _, kv = prepare_positive_map({k: sorted(v) for k, v in table.items()}, i.shape[1], kv, False)
+            i, _, _ = self._masked_ids(i, None if cap is None else (cap,), pm_key, lab, pm, dev)
+            ids.append(i)
+            ams.append(a)
+            kvs.append(kv)
+            pms.append(pm)
+            labs.append(lab)
+        T = ids[0].shape[1]
+        max_kv = max(kvs) if min(kvs) > 0 else 0
+        Tl = self._live_len(T, max_kv)
+        full_mask = torch.cat(ams)
+        input_ids, attention_mask = torch.cat(ids)[:, :Tl].contiguous(), full_mask[:, :Tl].contiguous()
+        vision = idx = None
+        if self._use_vq():
+            vision, idx = self.query_selector.select(labs, pms, Tl, dev, dtype)
+            if vision.shape[1] == 0:
+                vision = idx = None
+        feats, pooled = self._features(images)
+        front = pipeline.language_front(P, self.cfg, input_ids, attention_mask, vision is not None, max_kv=max_kv)
+        _, head, _ = self._head_operands(list(feats), pooled, front, input_ids, attention_mask, vision, idx, max_kv)
+        return criterion(head, self._anchors(feats), targets, positive_map, full_mask)
 
     # ------------------------------------------------------------------ chunk batching (SURVEY.md 8f-1)
     def _features(self, images):

@@ -86,12 +86,15 @@ _SIGNATURES = {
     "mq_bank_select_fwd": (_i, [_vp] * 6 + [_i] * 11 + [_vp]),
     "mq_bank_select_add_fwd": (_i, [_vp] * 5 + [_i] + [_vp] * 2 + [_i] * 11 + [_vp]),
     "mq_eval_rows": (_i, [_vp] * 6 + [_i] + [_vp] * 3 + [_i] * 4 + [_l, _i, _vp]),
+    "mq_atss_assign_fwd": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
+    "mq_atss_box_loss_fwd": (_i, [_vp] * 11 + [_i] * 3 + [_vp]),
+    "mq_token_focal_loss_fwd": (_i, [_vp] * 9 + [_i] * 6 + [_f, _f, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
               "mq_layernorm_fwd", "mq_layernorm2_fwd", "mq_layernorm_clamp_fwd", "mq_clamp_gelu_clamp", "mq_patch_merge_ln_fwd", "mq_swin_mlp2_fwd", "mq_conv3x3_fwd", "mq_conv3x3_nchw32_fwd", "mq_conv3x3_nchw32_v2_fwd", "mq_conv3x3_nchw32_group_fwd", "mq_dcnv2_fwd", "mq_dcnv2_group_fwd",
               "mq_dyconv_stats", "mq_dyconv_coef", "mq_dyconv_coef_group", "mq_dyconv_fuse", "mq_dyrelu_coef", "mq_dyconv_epilogue_group", "mq_dyconv_coef_relu_group", "mq_dyconv_fuse_act_group", "mq_dyrelu_apply", "mq_dyrelu_apply_group", "mq_dyrelu_ln_fwd", "mq_add_upsample_nearest", "mq_pool2x2_tokens_fwd",
-              "mq_align_scores_fwd", "mq_align_fused_fwd", "mq_box_decode", "mq_roi_align_fwd", "mq_msdeform_attn_fwd", "mq_msdeform_attn_q_fwd")
+              "mq_align_scores_fwd", "mq_align_fused_fwd", "mq_box_decode", "mq_roi_align_fwd", "mq_msdeform_attn_fwd", "mq_msdeform_attn_q_fwd", "mq_token_focal_loss_fwd")
 # ... and as <name>_f32 (fp32 operands, the precise mode), except ROIAlign: its base entry point already takes fp32 features (is_f32 flag) and has
 # no other 16-bit operand.  (Round 6: the MSDeformAttn kernels have the twin -- the fused-query form reads a 16-bit `qproj`, a float there.)
 F32_TWINS = tuple(n for n in BF16_TWINS if n not in ("mq_roi_align_fwd",))
@@ -1976,3 +1979,88 @@ def eval_rows(packed, counts, table, rows, state, cols=7, candidate=False, plus_
         _chk(lib.mq_eval_rows(_ptr(packed), _ptr(counts), _ptr(table), ctypes.c_void_p(table_host.data_ptr()), _ptr(lbl_keys), _ptr(lbl_vals), n_lbl,
                               _ptr(rows), _ptr(state), _ptr(state[1:]), E, items, K2, cols, capacity, flags, _stream()),
              "mq_eval_rows")
+
+
+# ---- the ATSS training objective, forward only (csrc/atss_loss.hip; host side: mq_det_amd/losses.py)
+ATSS_MAX_TOPK, ATSS_MAX_LEVELS, ATSS_BOX_SUMS = 64, 8, 5
+
+
+def _level_offsets(level_sizes, A):
+    offs = [0]
+    for n in level_sizes:
+        offs.append(offs[-1] + int(n))
+    if not 1 <= len(level_sizes) <= ATSS_MAX_LEVELS or offs[-1] != A:
+        raise ValueError(f"atss: {len(level_sizes)} levels of {offs[-1]} anchors for an anchor tensor of {A} rows (1 .. {ATSS_MAX_LEVELS} levels)")
+    return offs
+
+
+def atss_assign(anchors, level_sizes, gt, gt_off, B, topk=9):
+    """ATSS target assignment for a batch (mq_atss_assign_fwd): anchors [A, 4] fp32 with `level_sizes` anchors per level, gt [total, 4] fp32
+    packed image after image, gt_off [B + 1] int32 -> matched [B, A] int32 (the gt's index inside its image, -1 background)."""
+    lib = load_library()
+    _need_gpu(anchors, gt, gt_off)
+    assert anchors.dtype == gt.dtype == torch.float32 and gt_off.dtype == torch.int32 and anchors.dim() == 2 and anchors.shape[1] == 4
+    assert gt.dim() == 2 and gt.shape[1] == 4 and gt_off.numel() == B + 1 and anchors.is_contiguous() and gt.is_contiguous() and gt_off.is_contiguous()
+    A, G, NL = anchors.shape[0], gt.shape[0], len(level_sizes)
+    offs = _level_offsets(level_sizes, A)
+    if not 1 <= int(topk) <= ATSS_MAX_TOPK:
+        raise ValueError(f"atss: MODEL.ATSS.TOPK = {topk}, the kernel takes 1 .. {ATSS_MAX_TOPK}")
+    dev = anchors.device
+    thr = torch.empty(max(G, 1), dtype=torch.float32, device=dev)
+    kth = torch.empty(max(G, 1) * NL, dtype=torch.int64, device=dev)
+    matched = torch.empty(B, A, dtype=torch.int32, device=dev)
+    lvl = (ctypes.c_int * (NL + 1))(*offs)
+    with _timed("atss_assign", A * 16 * (B + 1) + G * 16 + B * A * 4):
+        _chk(lib.mq_atss_assign_fwd(_ptr(anchors), ctypes.cast(lvl, _vp), _ptr(gt), _ptr(gt_off), _ptr(thr), _ptr(kth), _ptr(matched), B, A, NL, G,
+                                    int(topk), _stream()), "mq_atss_assign_fwd")
+    return matched
+
+
+def atss_box_loss(anchors, gt, labels, gt_off, matched, reg=None, ctr=None, want_targets=False):
+    """Per-anchor targets and the box / centerness sums (mq_atss_box_loss_fwd).  labels [total] int64; matched [B, A] int32; reg [B, A, 4] and
+    ctr [B, A] fp32 (both or neither).  -> (sums [5] fp32 or None: positives, S ct, S ct (1 - GIoU), S BCE(ctr, ct), S (1 - GIoU);
+    cls_labels [B, A] int64 and reg_targets [B, A, 4] fp32, or None without want_targets)."""
+    lib = load_library()
+    _need_gpu(anchors, gt, labels, gt_off, matched, reg, ctr)
+    B, A = matched.shape
+    assert anchors.dtype == gt.dtype == torch.float32 and labels.dtype == torch.int64 and gt_off.dtype == matched.dtype == torch.int32
+    assert anchors.shape == (A, 4) and gt.dim() == 2 and gt.shape[1] == 4 and len(labels) == len(gt) and gt_off.numel() == B + 1
+    for t in (anchors, gt, labels, gt_off, matched):
+        assert t.is_contiguous()
+    assert (reg is None) == (ctr is None) and (reg is not None or want_targets)
+    dev = anchors.device
+    sums = partials = cls = tgt = None
+    if reg is not None:
+        assert reg.dtype == ctr.dtype == torch.float32 and reg.shape == (B, A, 4) and ctr.shape == (B, A) and reg.is_contiguous() and ctr.is_contiguous()
+        partials = torch.empty(B * (-(-A // 256)) * ATSS_BOX_SUMS, dtype=torch.float32, device=dev)
+        sums = torch.empty(ATSS_BOX_SUMS, dtype=torch.float32, device=dev)
+    if want_targets:
+        cls = torch.empty(B, A, dtype=torch.int64, device=dev)
+        tgt = torch.empty(B, A, 4, dtype=torch.float32, device=dev)
+    with _timed("atss_box_loss", B * A * (20 + (20 if reg is not None else 0) + (24 if want_targets else 0))):
+        _chk(lib.mq_atss_box_loss_fwd(_ptr(anchors), _ptr(gt), _ptr(labels), _ptr(gt_off), _ptr(matched), _ptr(reg), _ptr(ctr), _ptr(cls), _ptr(tgt),
+                                      _ptr(partials), _ptr(sums), B, A, len(gt), _stream()), "mq_atss_box_loss_fwd")
+    return sums, cls, tgt
+
+
+def token_focal_loss(tok, tk, tbias, matched, posmap, gt_off, text_mask, alpha, gamma, kv_max=0):
+    """The summed dot-product token focal loss on the operands of `align_fused` (mq_token_focal_loss_fwd): tok [B, N, 256] / tk [B, T, 256]
+    16-bit (fp32 in the precise mode), tbias [B, T] fp32, matched [B, N] int32, posmap [total, Tpm] fp32 (Tpm >= T: the caption's full
+    length), gt_off [B + 1] int32, text_mask [B, T] int32.  -> loss [1] fp32 on the device; the [B, N, T] logits are never written."""
+    lib = load_library()
+    _need_gpu(tok, tk, tbias, matched, posmap, gt_off, text_mask)
+    B, N, C = tok.shape
+    T = tk.shape[1]
+    assert C == 256 and tk.shape == (B, T, 256) and tok.is_contiguous() and tk.is_contiguous() and tok.dtype == tk.dtype and tok.dtype in _H16
+    assert tbias.dtype == posmap.dtype == torch.float32 and tbias.shape == (B, T) and tbias.is_contiguous()
+    assert matched.dtype == gt_off.dtype == text_mask.dtype == torch.int32 and matched.shape == (B, N) and text_mask.shape == (B, T)
+    assert posmap.dim() == 2 and posmap.shape[1] >= T and gt_off.numel() == B + 1
+    for t in (matched, posmap, gt_off, text_mask):
+        assert t.is_contiguous()
+    partials = torch.empty(B * (-(-N // 128)), dtype=torch.float32, device=tok.device)
+    loss = torch.empty(1, dtype=torch.float32, device=tok.device)
+    with _timed("token_focal_loss", tok.numel() * tok.element_size()):
+        _chk(_fn(lib, "mq_token_focal_loss_fwd", tok)(_ptr(tok), _ptr(tk), _ptr(tbias), _ptr(matched), _ptr(posmap), _ptr(gt_off), _ptr(text_mask),
+                                                      _ptr(partials), _ptr(loss), B, N, T, int(kv_max), posmap.shape[1], posmap.shape[0],
+                                                      float(alpha), float(gamma), _stream()), "mq_token_focal_loss_fwd")
+    return loss
