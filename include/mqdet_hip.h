@@ -402,7 +402,7 @@ int mq_msdeform_attn_q_fwd(const void* value, int value_f32, long value_bs, long
                            const long* level_start, const void* qproj, const float* ref, int ref_dim, const int* valid_hw,
                            void* out, int out_f32, int B, int S, int M, int D, int L, int Q, int P, void* stream);
 
-/* Class-aware NMS on score-sorted boxes, mask + sweep entirely on the device.
+/* Class-aware NMS on score-sorted boxes, mask + sweep entirely on the device (csrc/nms.hip: both entry points share the mask kernel and the sweep).
  *   boxes [B,N,4] fp32 (sorted by score desc per image), labels [B,N] int32, nvalid [B] int32 -> keep [B,N] uint8.
  * Replaces _C.ml_nms: maskrcnn_benchmark/csrc/ml_nms.h:10-27, csrc/cuda/ml_nms.cu:15-149 (vision.cpp:23). */
 long mq_ml_nms_workspace_bytes(int B, int N);
@@ -508,7 +508,7 @@ int mq_tta_merge_finalize_special(const float* boxes_m, const float* scores_m, c
                                   const unsigned char* keep, const int* nvalid, float* thr, const int* cls_rank, float* boxes_o,
                                   float* scores_o, long long* labels_o, int* counts, int B, int N, int top_n, void* stream);
 /* mq_tta_merge_nms: the per-class NMS of the 'none' merge at any row count, between mq_tta_merge_prep and mq_tta_merge_finalize: greedy
- *   suppression in list order between rows of equal label at iou > thresh (the +1 IoU of mq_ml_nms, operation for operation, uncontracted)
+ *   suppression in list order between rows of equal label at iou > thresh (the +1 IoU of mq_ml_nms: one function, csrc/box_iou.h, uncontracted)
  *   -> keep [B, N] uint8, all of it written, byte for byte what mq_ml_nms answers for the same lists -- without its B N^2 / 8 bytes of
  *   mask, which stop mq_ml_nms at 16 384 rows.  One workgroup per (image, class-list position 0 .. L - 1; L = length of cls_rank); the
  *   live rows' labels are inside the class list, as mq_tta_merge_prep leaves them.  A class of up to cap rows (1 .. 4096) is staged in

@@ -5,7 +5,7 @@
 //                         fp32 scores, ties at the cut resolved by the smaller flat index), decoded right away (BoxCoder.decode,
 //                         clip_to_image, sqrt score, label id -- vldyhead.py:78-108, inference.py:696-707) into the image's candidate list
 //   mq_post_sort_fwd      per image: the candidate list sorted by (score descending, candidate id ascending) -- the order ml_nms sweeps in
-//   mq_post_finalize_fwd  per image, after mq_ml_nms_topk: the first DETECTIONS_PER_IMG kept detections + those tied with the last of
+//   mq_post_finalize_fwd  per image, after mq_ml_nms_topk (nms.hip): the first DETECTIONS_PER_IMG kept detections + those tied with the last of
 //                         them (inference.py:757-766: kthvalue + `>=`) as one packed [K2, 6] block, the live count and the overflow flag
 //
 // Before: 5 x torch.topk(1000) (multi-block radix select: 13 launches each on the large levels), 5 x box_decode, argsort, 3 gathers,

@@ -7,7 +7,7 @@
 // weight 1 << 22), which gives the same bytes.  The kernel does integer math only, then the fp32 ToTensor / Normalize of the reference.
 //
 // mq_tta_merge_*: box_aug.py merge_result_from_multi_scales with SPECIAL_NMS = 'none', after the per-transform un-flip / area band /
-// rescale, as four launches around mq_ml_nms (post.hip).  Every sort is a rank by counting over a total order, so the result does not
+// rescale, as four launches around mq_ml_nms (nms.hip).  Every sort is a rank by counting over a total order, so the result does not
 // depend on the schedule.
 //
 // mq_tta_merge_special / mq_tta_merge_finalize_special: the same merge with SPECIAL_NMS = 'soft-nms', 'vote' or 'soft-vote': the per-class
@@ -18,6 +18,7 @@
 // TEST.USE_MULTISCALE: transforms x 5 x PRE_NMS_TOP_N rows per image), one workgroup per (image, class), the same keep flags byte for
 // byte (see "per-class NMS, any N" below).
 #include "common.h"
+#include "box_iou.h"
 
 MQ_NAMESPACE_BEGIN
 #ifdef MQ_PRIMARY_UNIT                                     // uint8 / fp32 / int data only: one copy, in the fp16 translation unit
@@ -332,6 +333,59 @@ extern "C" int mq_tta_merge_finalize(const float* boxes_s, const float* scores_s
 enum { TTA_SOFT_NMS = 1, TTA_VOTE = 2, TTA_SOFT_VOTE = 3 };
 enum { TTA_DEAD = 0, TTA_LIVE = 1, TTA_OUT = 4 };
 
+// The class segment of one workgroup (256 threads) of tta_special_kernel / tta_nms_kernel: lab = the labels of the image's score-sorted
+// list, n = min(max(nvalid[b], 0), N) its rows, c = the workgroup's position in the class list.
+// position of label l in the class list; -1: a label of no class (outside [0, L), or dropped by cls_rank)
+__device__ __forceinline__ int tta_cls_pos(const int* __restrict__ cls_rank, int L, int l) { return (l >= 0 && l < L) ? cls_rank[l] : -1; }
+
+// -> m, the rows of position c (the same in every thread), and st, where the workgroup stages them, WORDS words a row: the dynamic LDS
+// when m <= cap, else the class's slice of the workspace ws [B, N, WORDS] (counted in nws); the slice starts at the rows of the earlier
+// positions.  base = b * N; cnt_s: LDS int [2].
+template <int WORDS>
+__device__ __forceinline__ int tta_class_rows(const int* __restrict__ lab, const int* __restrict__ cls_rank, int L, int n, int c, int cap,
+                                              float* lds, float* ws, long base, int* nws, int* cnt_s, float*& st) {
+  const int tid = threadIdx.x;
+  if (tid < 2) cnt_s[tid] = 0;
+  __syncthreads();
+  int mc = 0, oc = 0;
+  for (int j = tid; j < n; j += 256) {
+    const int p = tta_cls_pos(cls_rank, L, lab[j]);
+    mc += p == c;
+    oc += p >= 0 && p < c;
+  }
+  atomicAdd(&cnt_s[0], mc);
+  atomicAdd(&cnt_s[1], oc);
+  __syncthreads();
+  const int m = cnt_s[0], off = cnt_s[1];
+  st = lds;
+  if (m > cap) {
+    if (tid == 0) atomicAdd(nws, 1);
+    st = ws + (base + off) * WORDS;
+  }
+  return m;
+}
+
+// store(j, k) for every row j of position c: k = the rows of the class before j in the list (a ballot prefix over the four waves: a
+// count, not a race).  wcnt: LDS int [4].
+template <class Store>
+__device__ __forceinline__ void tta_class_stage(const int* __restrict__ lab, const int* __restrict__ cls_rank, int L, int n, int c, int* wcnt,
+                                                Store store) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int run = 0;
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    const int j = j0 + tid;
+    const bool mine = j < n && tta_cls_pos(cls_rank, L, lab[j]) == c;
+    const unsigned long long bal = __ballot(mine);
+    if (lane == 0) wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    int k = run + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wv; ++w) k += wcnt[w];
+    run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    if (mine) store(j, k);
+    __syncthreads();
+  }
+}
+
 __device__ __forceinline__ float tta_iou1(float ax1, float ay1, float ax2, float ay2, float aa, float bx1, float by1, float bx2, float by2,
                                           float ba) {
 #pragma clang fp contract(off)                           // soft_nms.cpp:77-86 / box_aug.py:252-260, one operation at a time
@@ -354,59 +408,33 @@ __global__ __launch_bounds__(256) void tta_special_kernel(const float* __restric
                                                           const int* __restrict__ nvalid, const int* __restrict__ cls_rank,
                                                           float* __restrict__ boxes_m, float* __restrict__ scores_m,
                                                           unsigned char* __restrict__ keep, int* __restrict__ seq, float* __restrict__ ws,
-                                                          int* __restrict__ nws, int N, int mode, float thresh, float aux, int cap) {
+                                                          int* __restrict__ nws, int N, int L, int mode, float thresh, float aux, int cap) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) float sp_s[];             // [TTA_SP_WORDS][m] when the class fits
   __shared__ int cnt_s[2], wcnt[4], red_k[4], red_r[4];
   __shared__ float red_s[4];
   __shared__ double red_d[5][4];
-  const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = nvalid[b];
+  const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = min(max(nvalid[b], 0), N);
   const long base = (long)b * N;
-  // rows of this class (m) and of the classes before it in the list (off)
-  if (tid < 2) cnt_s[tid] = 0;
-  __syncthreads();
-  int mc = 0, oc = 0;
-  for (int j = tid; j < n; j += 256) {
-    const int p = cls_rank[labels_s[base + j]];
-    mc += p == c;
-    oc += p < c;
-  }
-  atomicAdd(&cnt_s[0], mc);
-  atomicAdd(&cnt_s[1], oc);
-  __syncthreads();
-  const int m = cnt_s[0], off = cnt_s[1];
+  const int* lab = labels_s + base;
+  float* st;
+  const int m = tta_class_rows<TTA_SP_WORDS>(lab, cls_rank, L, n, c, cap, sp_s, ws, base, nws, cnt_s, st);
   if (m == 0) return;
-  const bool in_lds = m <= cap;
-  if (!in_lds && tid == 0) atomicAdd(nws, 1);
-  float* st = in_lds ? sp_s : ws + (base + off) * TTA_SP_WORDS;
   float *X1 = st, *Y1 = st + m, *X2 = st + 2 * (long)m, *Y2 = st + 3 * (long)m, *AR = st + 4 * (long)m, *SC = st + 5 * (long)m;
   int *IDX = (int*)(st + 6 * (long)m), *SRC = (int*)(st + 7 * (long)m), *FL = (int*)(st + 8 * (long)m);
-  // stage: row j of the list goes to slot (rows of the class before j)
-  int run = 0;
-  for (int j0 = 0; j0 < n; j0 += 256) {
-    const int j = j0 + tid;
-    const bool mine = j < n && cls_rank[labels_s[base + j]] == c;
-    const unsigned long long bal = __ballot(mine);
-    if (lane == 0) wcnt[wv] = __popcll(bal);
-    __syncthreads();
-    int k = run + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wv; ++w) k += wcnt[w];
-    run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    if (mine) {
-      const float x1 = boxes_s[(base + j) * 4 + 0], y1 = boxes_s[(base + j) * 4 + 1], x2 = boxes_s[(base + j) * 4 + 2],
-                  y2 = boxes_s[(base + j) * 4 + 3];
-      X1[k] = x1;
-      Y1[k] = y1;
-      X2[k] = x2;
-      Y2[k] = y2;
-      AR[k] = ((x2 - x1) + 1.f) * ((y2 - y1) + 1.f);
-      SC[k] = scores_s[base + j];
-      IDX[k] = j;
-      SRC[k] = src_s[base + j];
-      FL[k] = TTA_LIVE;
-    }
-    __syncthreads();
-  }
+  tta_class_stage(lab, cls_rank, L, n, c, wcnt, [&](int j, int k) {
+    const float x1 = boxes_s[(base + j) * 4 + 0], y1 = boxes_s[(base + j) * 4 + 1], x2 = boxes_s[(base + j) * 4 + 2],
+                y2 = boxes_s[(base + j) * 4 + 3];
+    X1[k] = x1;
+    Y1[k] = y1;
+    X2[k] = x2;
+    Y2[k] = y2;
+    AR[k] = ((x2 - x1) + 1.f) * ((y2 - y1) + 1.f);
+    SC[k] = scores_s[base + j];
+    IDX[k] = j;
+    SRC[k] = src_s[base + j];
+    FL[k] = TTA_LIVE;
+  });
 
   if (mode == TTA_SOFT_NMS) {
     const double sigma = (double)aux;
@@ -565,7 +593,7 @@ extern "C" int mq_tta_merge_special(const float* boxes_s, const float* scores_s,
   if (N > cap && !ws) return -1;
   const size_t smem = (size_t)(cap < N ? cap : N) * TTA_SP_WORDS * sizeof(float);
   return mq_launch<tta_special_kernel>(dim3(L, B), dim3(256), smem, (hipStream_t)stream, boxes_s, scores_s, labels_s, src_s, nvalid, cls_rank,
-                                       boxes_m, scores_m, keep, seq, ws, nws, N, mode, thresh, aux, cap);
+                                       boxes_m, scores_m, keep, seq, ws, nws, N, L, mode, thresh, aux, cap);
 }
 
 // mq_tta_merge_finalize for the rows of mq_tta_merge_special: the cut over the new scores, then the output order (class-list position, seq).
@@ -584,10 +612,11 @@ extern "C" int mq_tta_merge_finalize_special(const float* boxes_m, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- per-class NMS, any N
-// mq_tta_merge_nms: what mq_ml_nms (post.hip) answers -- greedy suppression in list order between rows of equal label at iou > thresh --
-// without its [N, N / 64] bit mask, for the candidate lists of TEST.USE_MULTISCALE (transforms x 5 x PRE_NMS_TOP_N rows per image).  Built
-// like tta_special_kernel: one workgroup per (image, class-list position), the class's rows gathered in list order and staged -- box,
-// +1 area, list index -- in LDS, or in the class's own slice of a global workspace when it has more than `cap` rows.
+// mq_tta_merge_nms: what mq_ml_nms (nms.hip) answers -- greedy suppression in list order between rows of equal label at iou > thresh --
+// without its [N, N / 64] bit mask, for the candidate lists of TEST.USE_MULTISCALE (transforms x 5 x PRE_NMS_TOP_N rows per image).  The
+// class segment of tta_special_kernel (tta_class_rows / tta_class_stage): one workgroup per (image, class-list position), the class's rows
+// gathered in list order and staged -- box, +1 area, list index -- in LDS, or in the class's own slice of a global workspace when it has
+// more than `cap` rows.
 // The sweep takes 256 rows at a time, one per thread:
 //   a. every row is tested against the heads kept so far (a compact list, read at the same address by every lane; no barrier per head),
 //   b. the four waves resolve their 64 rows one after the other: row j of the wave is final once rows 0 .. j - 1 are, and a kept j
@@ -596,18 +625,8 @@ extern "C" int mq_tta_merge_finalize_special(const float* boxes_m, const float* 
 // The kept list is compacted IN PLACE over the staged rows (kept head k <= its own row's slot, and every thread holds its row in
 // registers from the top of the chunk); in the workspace path the first 6 * cap / 5 heads live in the idle LDS instead.
 // Every decision is taken on final flags behind a barrier or inside one wave in lane order: no race decides an order.  The IoU is
-// ml_iou2 (nms2.hip) operation for operation with contraction off (post.hip's compile does not contract it either).
+// box_iou_area (box_iou.h), the one nms.hip's mask kernel evaluates.
 #define TTA_NMS_WORDS 6                                    // 4-byte words staged per row: x1 y1 x2 y2 area index
-
-__device__ __forceinline__ float tta_iou2(float ax1, float ay1, float ax2, float ay2, float sa, float bx1, float by1, float bx2, float by2,
-                                          float sb) {
-#pragma clang fp contract(off)
-  const float left = fmaxf(ax1, bx1), right = fminf(ax2, bx2);
-  const float top = fmaxf(ay1, by1), bottom = fminf(ay2, by2);
-  const float w = fmaxf(right - left + 1.f, 0.f), h = fmaxf(bottom - top + 1.f, 0.f);
-  const float inter = w * h;
-  return inter / (sa + sb - inter);
-}
 
 __global__ __launch_bounds__(256) void tta_nms_kernel(const float* __restrict__ boxes_s, const int* __restrict__ labels_s,
                                                       const int* __restrict__ nvalid, const int* __restrict__ cls_rank,
@@ -619,57 +638,31 @@ __global__ __launch_bounds__(256) void tta_nms_kernel(const float* __restrict__ 
   const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = min(max(nvalid[b], 0), N);
   const long base = (long)b * N;
   for (long j = (long)n + c * 256 + tid; j < N; j += (long)L * 256) keep[base + j] = 0;   // rows past the list: not kept (the blocks of an image share them out)
-  if (tid < 2) cnt_s[tid] = 0;
+  const int* lab = labels_s + base;
+  if (c == 0)                                              // a label outside the class list (mq_tta_merge_prep leaves none): not kept
+    for (int j = tid; j < n; j += 256)
+      if (tta_cls_pos(cls_rank, L, lab[j]) < 0) keep[base + j] = 0;
   if (tid == 0) nk_s = 0;
-  __syncthreads();
-  int mc = 0, oc = 0;
-  for (int j = tid; j < n; j += 256) {
-    const int l = labels_s[base + j], p = (l >= 0 && l < L) ? cls_rank[l] : -1;
-    mc += p == c;
-    oc += p >= 0 && p < c;
-    if (c == 0 && p < 0) keep[base + j] = 0;               // a label outside the class list (mq_tta_merge_prep leaves none): not kept
-  }
-  atomicAdd(&cnt_s[0], mc);
-  atomicAdd(&cnt_s[1], oc);
-  __syncthreads();
-  const int m = cnt_s[0], off = cnt_s[1];
+  float* st;
+  const int m = tta_class_rows<TTA_NMS_WORDS>(lab, cls_rank, L, n, c, cap, sp_s, ws, base, nws, cnt_s, st);
   if (m == 0) return;
   const bool in_lds = m <= cap;
-  if (!in_lds && tid == 0) atomicAdd(nws, 1);
-  float* st = in_lds ? sp_s : ws + (base + off) * TTA_NMS_WORDS;
   float *X1 = st, *Y1 = st + m, *X2 = st + 2 * (long)m, *Y2 = st + 3 * (long)m, *AR = st + 4 * (long)m;
   int* IDX = (int*)(st + 5 * (long)m);
   // kept heads: slot k < kc in K*, the rest in place in the staged arrays (the LDS path: all of them, K* == the staged arrays)
   const int kc = in_lds ? m : (cap * TTA_NMS_WORDS) / 5;
   float *K1 = in_lds ? X1 : sp_s, *K2 = in_lds ? Y1 : sp_s + kc, *K3 = in_lds ? X2 : sp_s + 2 * kc, *K4 = in_lds ? Y2 : sp_s + 3 * kc,
         *KA = in_lds ? AR : sp_s + 4 * kc;
-  // stage: row j of the list goes to slot (rows of the class before j)
-  int run = 0;
-  for (int j0 = 0; j0 < n; j0 += 256) {
-    const int j = j0 + tid;
-    bool mine = false;
-    if (j < n) {
-      const int l = labels_s[base + j];
-      mine = l >= 0 && l < L && cls_rank[l] == c;
-    }
-    const unsigned long long bal = __ballot(mine);
-    if (lane == 0) wcnt[wv] = __popcll(bal);
-    __syncthreads();
-    int k = run + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wv; ++w) k += wcnt[w];
-    run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    if (mine) {
-      const float x1 = boxes_s[(base + j) * 4 + 0], y1 = boxes_s[(base + j) * 4 + 1], x2 = boxes_s[(base + j) * 4 + 2],
-                  y2 = boxes_s[(base + j) * 4 + 3];
-      X1[k] = x1;
-      Y1[k] = y1;
-      X2[k] = x2;
-      Y2[k] = y2;
-      AR[k] = (x2 - x1 + 1.f) * (y2 - y1 + 1.f);
-      IDX[k] = j;
-    }
-    __syncthreads();
-  }
+  tta_class_stage(lab, cls_rank, L, n, c, wcnt, [&](int j, int k) {
+    const float x1 = boxes_s[(base + j) * 4 + 0], y1 = boxes_s[(base + j) * 4 + 1], x2 = boxes_s[(base + j) * 4 + 2],
+                y2 = boxes_s[(base + j) * 4 + 3];
+    X1[k] = x1;
+    Y1[k] = y1;
+    X2[k] = x2;
+    Y2[k] = y2;
+    AR[k] = (x2 - x1 + 1.f) * (y2 - y1 + 1.f);
+    IDX[k] = j;
+  });
 
   int nk = 0;                                              // kept heads so far (the same in every thread)
   for (int r0 = 0; r0 < m; r0 += 256) {
@@ -684,16 +677,16 @@ __global__ __launch_bounds__(256) void tta_nms_kernel(const float* __restrict__ 
         int k = done;
         const int k_lds = min(nk, kc);
         for (; alive && k < k_lds; ++k)
-          if (tta_iou2(K1[k], K2[k], K3[k], K4[k], KA[k], x1, y1, x2, y2, ar) > thresh) alive = 0;
+          if (box_iou_area(K1[k], K2[k], K3[k], K4[k], KA[k], x1, y1, x2, y2, ar) > thresh) alive = 0;
         for (k = max(k, kc); alive && k < nk; ++k)
-          if (tta_iou2(X1[k], Y1[k], X2[k], Y2[k], AR[k], x1, y1, x2, y2, ar) > thresh) alive = 0;
+          if (box_iou_area(X1[k], Y1[k], X2[k], Y2[k], AR[k], x1, y1, x2, y2, ar) > thresh) alive = 0;
         done = nk;
       }
       if (wv == s) {
         for (int j = 0; j < 64; ++j) {                     // row j of the wave is final here: rows 0 .. j - 1 have had their say
           const int aj = __shfl(alive, j);
           const float jx1 = __shfl(x1, j), jy1 = __shfl(y1, j), jx2 = __shfl(x2, j), jy2 = __shfl(y2, j), ja = __shfl(ar, j);
-          if (aj && alive && lane > j && tta_iou2(jx1, jy1, jx2, jy2, ja, x1, y1, x2, y2, ar) > thresh) alive = 0;
+          if (aj && alive && lane > j && box_iou_area(jx1, jy1, jx2, jy2, ja, x1, y1, x2, y2, ar) > thresh) alive = 0;
         }
         const unsigned long long bal = __ballot(alive);
         if (have) keep[base + idx] = (unsigned char)alive;

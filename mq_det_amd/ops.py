@@ -1612,9 +1612,9 @@ def ml_nms(boxes, labels, nvalid, thresh, max_keep=0, as_bool=True):
     if max_keep > 0 and N <= 6656 and KERNELS["NMS_EARLY_STOP"] == 1:
         _chk(lib.mq_ml_nms_topk(_ptr(boxes), _ptr(labels), _ptr(nvalid), _ptr(ws), _ptr(keep), B, N, float(thresh), int(max_keep), _stream()),
              "mq_ml_nms_topk")
-        return keep.bool() if as_bool else keep
-    _chk(lib.mq_ml_nms(_ptr(boxes), _ptr(labels), _ptr(nvalid), _ptr(ws), _ptr(keep), B, N, float(thresh), _stream()),
-         "mq_ml_nms")
+    else:
+        _chk(lib.mq_ml_nms(_ptr(boxes), _ptr(labels), _ptr(nvalid), _ptr(ws), _ptr(keep), B, N, float(thresh), _stream()),
+             "mq_ml_nms")
     return keep.bool() if as_bool else keep
 
 

@@ -1140,6 +1140,62 @@ def check_nms(dev):
     return res
 
 
+NMS_DISPATCH_SIZES = (4096, 4097, 6656, 6657, 8192, 8193)     # 64 | 65, 104 | 105, 128 | 129 column blocks: every boundary of the sweep dispatch
+
+
+def check_nms_dispatch(dev, sizes=None):
+    """The sweep mq_ml_nms / mq_ml_nms_topk pick at each boundary of the dispatch (csrc/nms.hip: LDS sweep <1> up to 64 column blocks,
+    <2> up to 104, the one-wave sweep <2> up to 128, then <4>; the early stop up to 104), inputs drawn as in check_nms:
+    the full sweep against the oracle, the early stop as a prefix of it, mq_tta_merge_nms (the same IoU, csrc/box_iou.h) byte for byte.
+    The emulator runs the two smallest sizes (each larger one takes minutes there)."""
+    from oracle import postprocess as op
+    from mq_det_amd import ops
+    if sizes is None:
+        sizes = NMS_DISPATCH_SIZES[:2] if dev.type == "cpu" else NMS_DISPATCH_SIZES
+    g = torch.Generator().manual_seed(23)
+    res = []
+
+    def row(name, ok):
+        res.append({"name": name, "max_err": 0.0 if ok else 1.0, "mean_err": 0.0, "ref_absmax": 1.0, "norm_err": 0.0 if ok else 1.0,
+                    "tol": 0.0, "ok": bool(ok)})
+
+    for N in sizes:
+        B = 2
+        xy = torch.rand(B, N, 2, generator=g) * 300
+        wh = torch.rand(B, N, 2, generator=g) * 120 + 4
+        boxes = torch.cat([xy, xy + wh], -1)
+        scores = torch.rand(B, N, generator=g)
+        labels = torch.randint(1, 6, (B, N), generator=g).int()
+        order = torch.argsort(scores, dim=1, descending=True, stable=True)
+        boxes = torch.gather(boxes, 1, order[:, :, None].expand(-1, -1, 4)).contiguous()
+        labels = torch.gather(labels, 1, order).contiguous()
+        scores = torch.gather(scores, 1, order)
+        nvalid = torch.tensor([N, N - 7], dtype=torch.int32)
+        bd, ld, nd = boxes.to(dev), labels.to(dev), nvalid.to(dev)
+        full = ops.ml_nms(bd, ld, nd, 0.6, as_bool=False).cpu()
+        ok = True
+        for b in range(B):
+            nv = int(nvalid[b])
+            ref = torch.zeros(N, dtype=torch.bool)
+            ref[op.ml_nms(boxes[b, :nv], scores[b, :nv], labels[b, :nv].float(), 0.6)] = True
+            ok &= bool(torch.equal(ref, full[b].bool()))
+        row(f"ml_nms N={N} ({(N + 63) // 64} column blocks) vs the oracle", ok)
+        for K in (1, 300):
+            part = ops.ml_nms(bd, ld, nd, 0.6, max_keep=K, as_bool=False).cpu()
+            ok = True
+            for b in range(B):
+                kf, kp = full[b].nonzero().flatten(), part[b].nonzero().flatten()
+                n = min(K, len(kf))
+                ok &= len(kp) >= n and bool(torch.equal(kp[:n], kf[:n])) and bool((part[b] <= full[b]).all())
+            if N > 6656:                                   # past the early stop's sweep the wrapper takes the full one
+                ok &= bool(torch.equal(part, full))
+            row(f"ml_nms N={N} max_keep={K}: the first survivors of the full sweep, nothing else", ok)
+        cls_rank = torch.tensor([-1, 0, 1, 2, 3, 4], dtype=torch.int32)
+        seg = ops.tta_merge_nms(bd, ld, nd, cls_rank.to(dev), 0.6).cpu()
+        row(f"tta_merge_nms N={N}: the bytes of ml_nms", torch.equal(seg, full))
+    return res
+
+
 def make_inputs(spec, B=2, hw=((150, 190), (160, 170)), nvalid=30, seed=3):
     from oracle import detector as od
     from oracle.weights import make_query_bank
@@ -1259,6 +1315,7 @@ def all_checks(dev):
             ("layernorm", lambda: check_layernorm(dev)),
             ("dyconv", lambda: check_dyconv(dev)),
             ("nms", lambda: check_nms(dev)),
+            ("nms", lambda: check_nms_dispatch(dev)),
             ("swin-L", lambda: check_window_attention(dev, large=True)),
             ("swin-L", lambda: check_swin_fpn(dev, large=True)),
             ("full", lambda: check_full_model(dev)),

@@ -104,6 +104,13 @@ def test_block(dev, name):
     _assert(getattr(pc, name)(dev))
 
 
+@pytest.mark.parametrize("N", [4096, 4097, 6656, 6657, 8192, 8193])
+def test_nms_dispatch(dev, N):
+    """Every boundary of the NMS sweep dispatch (64 | 65, 104 | 105, 128 | 129 column blocks): full sweep, early stop, mq_tta_merge_nms."""
+    import parity_checks as pc
+    _assert(pc.check_nms_dispatch(dev, sizes=(N,)))
+
+
 def test_full_model_without_vision_queries(dev):
     """Plain GLIP-T path (no query bank), B = 1 -- BASELINE.json configs[0] shape."""
     import parity_checks as pc

@@ -169,7 +169,7 @@ def test_attention_strided_views(kernels):
 
 
 @pytest.mark.parametrize("name", ["check_window_attention", "check_gcp_block", "check_pre_select", "check_vlfuse_kernels", "check_vl_fuse",
-                                  "check_dcn", "check_dyconv", "check_post_golden", "check_score_agg", "check_layernorm", "check_nms", "check_swin_mlp",
+                                  "check_dcn", "check_dyconv", "check_post_golden", "check_score_agg", "check_layernorm", "check_nms", "check_nms_dispatch", "check_swin_mlp",
                                   "check_conv3x3", "check_roi_align", "check_msdeform_attn", "check_swin_fpn", "check_align_fused", "check_post_fused", "check_attention_text", "check_bert_attn_qkv", "check_gcp_attn_fused", "check_patch_embed", "check_bert_clamp_fused"])
 def test_kernel_block(kernels, name):
     _assert_ok(getattr(kernels, name)(CPU))
@@ -735,7 +735,7 @@ def test_fpn_convs_through_the_grouped_dcn_kernel(kernels, monkeypatch):
             assert torch.equal(a, b)
 
 
-# ---- NMS that stops once max_keep boxes of an image are kept (csrc/nms2.hip, opt-in: MQ_NMS_EARLY_STOP=1)
+# ---- NMS that stops once max_keep boxes of an image are kept (csrc/nms.hip, opt-in: MQ_NMS_EARLY_STOP=1)
 def test_nms_early_stop_keeps_the_same_top_detections(kernels, monkeypatch):
     """score-sorted input: the first max_keep survivors of mq_ml_nms_topk are those of mq_ml_nms, nothing is kept behind the stopping
     chunk, images of one batch stop at different chunks; under permuted wave schedules (the stop flag is read by all five waves of the
