@@ -650,6 +650,32 @@ int mq_token_focal_loss_fwd(const void* tok, const void* tk, const float* tbias,
                             const int* text_mask, float* partials, float* loss, int B, int N, int T, int kv_max, int Tpm, int total_gt,
                             float alpha, float gamma, void* stream);
 
+/* ---- The set criterion of MQ-GroundingDINO, forward only (csrc/set_loss.hip, host side mq_det_amd/set_loss.py; GroundingDINO/matcher.py:49-86,
+ * loss.py:42-91).  fp32 operands only (no twins).  L decoder layers, B images, nq queries, T text positions of the logits, Tpm >= T width of the
+ * positive map; gts packed image after image: gt [total_gt, 4] fp32 normalised cxcywh, posmap [total_gt, Tpm] fp32 (> 0: positive),
+ * gt_off [B + 1] int32 (device).  No floating-point atomics: a result is the same bits from run to run.
+ *
+ * mq_set_cost_fwd: logits [L, B, nq, T] fp32 pre-sigmoid (-inf at padded text positions), boxes [L, B, nq, 4] fp32 cxcywh -> cost fp32, for layer l
+ * and image b a row-major [G_b, nq] block at element offset (l total_gt + gt_off[b]) nq (gt-major):
+ *   cost_bbox L1 + cost_class mean over the gt's positive tokens of (pos - neg) + cost_giou (-GIoU),
+ * pos / neg the focal terms of matcher.py:63-64 (gamma = 2, their 1e-8), GIoU with box_ops.py's two 1e-6.  A positive token at a column >= T or at
+ * a -inf logit has p = 0 and still counts in the mean; a gt without positive tokens gives a NaN row (the reference's empty mean).
+ * T <= 512; -1: bad sizes. */
+int mq_set_cost_fwd(const float* logits, const float* boxes, const float* gt, const float* posmap, const int* gt_off, float* cost, int L, int B,
+                    int nq, int T, int Tpm, int total_gt, float cost_class, float cost_bbox, float cost_giou, float focal_alpha, void* stream);
+/* The minimum-cost assignment of every [G_b, nq] block of `cost` (all L B problems in one launch; Crouse's shortest augmenting paths, duals and
+ * path costs in fp64, an argmin tie to the lower column) -> match_q [L, total_gt] int32 (the query of each gt), q2g [L, B, nq] int32 (the gt's index
+ * inside its image, -1 unmatched).  G_b = 0: q2g stays -1.  A problem that reads a non-finite entry gets -1 for all its gts.
+ * max_gt = the largest G_b (the host knows the counts).  -2: nq > 1024; -3: max_gt > nq; -1: other bad sizes. */
+int mq_hungarian_fwd(const float* cost, const int* gt_off, int* match_q, int* q2g, int L, int B, int nq, int total_gt, int max_gt, void* stream);
+/* loss_labels / loss_boxes as raw sums per layer -> sums [L, 3] fp32 = (token focal sum, S |src - tgt| and S (1 - GIoU) over the matched pairs).
+ * text_mask [B, T] int32: a column whose mask is 0 is skipped before any arithmetic.  The token target of a matched query is posmap[gt] > 0
+ * (a matched gt without positive tokens: the background target), of an unmatched one 1 at column Tpm - 1 only.  alpha < 0: no alpha_t factor.
+ * An image whose match_q rows are -1 (the solver gave up) makes the layer's three sums NaN.  partials [L ceil(B nq / 16), 3] workspace. */
+int mq_set_loss_fwd(const float* logits, const float* boxes, const float* gt, const float* posmap, const int* gt_off, const int* text_mask,
+                    const int* q2g, const int* match_q, float* partials, float* sums, int L, int B, int nq, int T, int Tpm, int total_gt,
+                    float alpha, float gamma, void* stream);
+
 /* MFMA B-FRAGMENT ORDER of a weight matrix W [N, K] (N % 16 == 0, K % 32 == 0; ABI 28): the same elements as the row-major nn.Linear weight,
  * re-ordered ONCE when the checkpoint is loaded to [N / 16][K / 32][64][8] --
  *     packed[((n / 16) * (K / 32) + k / 32) * 512 + ((k % 32) / 8 * 16 + n % 16) * 8 + k % 8] = W[n][k]

@@ -8,6 +8,7 @@ PyTorch is used for device memory, streams, library GEMMs/convs and torch.distri
 from .config import CfgNode, get_cfg  # noqa: F401
 from .structures import BoxList, ImageList, to_image_list, cat_boxlist  # noqa: F401
 from .losses import ATSSLoss, evaluate_loss, prepare_targets  # noqa: F401
+from .set_loss import SetCriterionLoss, hungarian_match, validate_set_loss_config  # noqa: F401
 
 
 def build_detection_model(cfg, **kwargs):

@@ -138,7 +138,8 @@ def get_cfg():
         AUGMENT_IMAGE_WITH_QUERY=False, RETURN_ATTN_GATE_VALUE=False, EXPAND_RATIO=1.5, MAX_QUERY_NUMBER=5000,
         SIMILARITY_THRESHOLD=0.85,
         # the bank-building and test-time online-update loops (mq_det_amd.query_bank; defaults.py:903-935)
-        DATASET_NAME="", MAX_TEST_QUERY_NUMBER=100, SCORE_THRESHOLD=0.6, NUM_TURNS=1, QUERY_ADDITION_NAME="", QUERY_BANK_SAVE_PATH=""))
+        DATASET_NAME="", MAX_TEST_QUERY_NUMBER=100, SCORE_THRESHOLD=0.6, NUM_TURNS=1, QUERY_ADDITION_NAME="", QUERY_BANK_SAVE_PATH="",
+        GATE_REGULARIZATION=False, GATE_REGULARIZATION_SCALE=0.1))                                      # :914-915, read by loss_gate
     cfg.TEST = C(dict(IMS_PER_BATCH=8, CHUNKED_EVALUATION=-1, MDETR_STYLE_AGGREGATE_CLASS_NUM=-1,
                       USE_MULTISCALE=False, EVAL_TASK="detection",
                       # test-time augmentation, read by mq_det_amd.tta.im_detect_bbox_aug (defaults.py:855-866)
@@ -161,7 +162,10 @@ def get_cfg():
         dec_pred_bbox_embed_share=True, embed_init_tgt=True, max_text_len=256, text_encoder_type="bert-base-uncased",
         use_text_enhancer=True, use_fusion_layer=True, use_checkpoint=False, use_transformer_ckpt=False,
         use_text_cross_attention=True, text_dropout=0.0, fusion_dropout=0.0, fusion_droppath=0.1, sub_sentence_present=True,
-        box_threshold=0.05))
+        box_threshold=0.05,
+        # the set criterion mq_det_amd.set_loss reads (:988-1001)
+        focal_alpha=0.25, loss_ce_coef=2.0, loss_bbox_coef=5.0, loss_giou_coef=2.0,
+        matcher=dict(matcher_type="HungarianMatcher", set_cost_class=1.0, set_cost_bbox=5.0, set_cost_giou=2.0, focal_alpha=0.25)))
     return cfg
 
 

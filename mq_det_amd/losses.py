@@ -243,7 +243,11 @@ def evaluate_loss(model, data_loader, device="cuda"):
     """Dataset means of the three losses from the raw sums: sum over batches first, normalise once -- loss_reg = REG_LOSS_WEIGHT S ct (1 - GIoU)
     / S ct, loss_centerness = S BCE / max(positives, 1), loss_dot_product_token = WEIGHT S focal / max(positives, 1).  A batch is
     (images, targets, ...) as the reference's loaders yield it; captions come from the targets' 'caption' field, the positive map from their
-    'positive_map' field.  ONE host synchronisation, at the end.  -> dict of floats (+ 'num_pos', 'batches')."""
+    'positive_map' field.  ONE host synchronisation, at the end.  -> dict of floats (+ 'num_pos', 'batches').
+    An MQ-GroundingDINO model (cfg.GROUNDINGDINO.enabled) is evaluated on its set criterion instead: set_loss.evaluate_set_loss."""
+    if model.cfg.get("GROUNDINGDINO", {}).get("enabled", False):
+        from .set_loss import evaluate_set_loss
+        return evaluate_set_loss(model, data_loader, device)
     model.eval()
     crit = ATSSLoss(model.cfg)
     total, n = None, 0

@@ -181,6 +181,69 @@ class GroundingDINO(DeviceModel):
             return result, feats
         return result
 
+    # ------------------------------------------------------------------ the training objective, forward only (mq_det_amd/set_loss.py)
+    @torch.no_grad()
+    def forward_losses(self, samples, targets, captions=None, positive_map=None):
+        """The set criterion of the reference's training forward (groundingdino.py:608-641, loss.py, matcher.py) on the DETERMINISTIC
+        EVAL-MODE forward: no autograd, no dropout, `model.train()` keeps raising.  targets: one BoxList per image (xyxy or with a
+        'normed_cxcy_boxes' field; 'labels' when a query bank is loaded); captions: one string per image, default the targets' 'caption'
+        fields; positive_map [sum of gts, max_text_len], default the concatenation of the targets' 'positive_map' fields (binarised, as the
+        reference does).  Runs the eval program, eagerly, through the decoder with the per-layer states kept, then `SetCriterionLoss`
+        instead of the detection heads.  The label -> token table the vision-query selection needs is read ON THE HOST from the labels and
+        positive-map rows: pass them as the loader yields them (CPU tensors) and the call makes no device->host transfer.
+        -> the reference's dict (`loss_ce`, `loss_bbox`, `loss_giou`, `loss_*_{i}` of the aux layers, `loss_gate` with vision queries) plus
+        `sums` [L, 3], `num_boxes`, `match_q`, `q2g`, on the device."""
+        if self.training:
+            raise NotImplementedError("training forward is out of scope")
+        from ..set_loss import SetCriterionLoss
+        criterion = SetCriterionLoss(self.cfg)                    # refuses unsupported settings by name, before anything is launched
+        V = self.cfg.VISION_QUERY
+        if V.ENABLED and V.get("RETURN_ATTN_GATE_VALUE", False):
+            raise NotImplementedError("VISION_QUERY.RETURN_ATTN_GATE_VALUE: the reference's gate term indexes a Python float there")
+        images = to_image_list(samples)
+        dev = images.tensors.device
+        Bn, _, H, W = images.tensors.shape
+        if captions is None:
+            captions = [t.get_field("caption") for t in targets]
+        captions = [captions] * Bn if isinstance(captions, str) else list(captions)
+        if len(targets) != Bn or len(captions) != Bn:
+            raise ValueError(f"forward_losses: {Bn} images, {len(targets)} targets, {len(captions)} captions")
+        captions = [preprocess_caption(c) for c in captions]
+        if positive_map is None:
+            if not all("positive_map" in t.fields() for t in targets):
+                raise ValueError("forward_losses: no positive_map given and the targets carry no 'positive_map' field")
+            positive_map = torch.cat([t.get_field("positive_map") for t in targets], 0)
+        positive_map = (positive_map > 0).float()                 # groundingdino.py:612
+        P = self._ensure_plan(dev)
+        dtype = P["backbone.0.patch_embed.proj.weight"].dtype
+        sizes = tuple((int(h), int(w)) for h, w in images.image_sizes)
+        geo = self._geo_cache.get((H, W, sizes, str(dev)), lambda: gp.geometry(P, self.cfg, H, W, sizes, dev))
+        txt, max_kv = self._text(captions, dev)
+        vision = idx = None
+        if self._use_vq():
+            table = {}                                            # {label: token positions} over the batch, for the vision queries
+            labels = torch.cat([t.get_field("labels").reshape(-1) for t in targets]).tolist()
+            for r, c in positive_map.nonzero().tolist():
+                table.setdefault(int(labels[r]), set()).add(c)
+            pm, labels_in_caption, pm_key = prepare_positive_map({k: sorted(table[k]) for k in sorted(table)}, self.max_text_len)[:3]
+            vision, idx = self.query_selector.select_cached(pm_key, labels_in_caption, pm, Bn, self.cfg.MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN,
+                                                            dev, dtype)
+            if vision.shape[1] == 0:
+                vision = idx = None
+        x = images.tensors.to(dtype).contiguous(memory_format=torch.channels_last)
+        out = gp.forward_device(P, self.cfg, self._swin, x, geo, txt, vision, idx, None, None, max_kv=int(max_kv), want_set=True)
+        logits, boxes = out["set_logits"], out["set_boxes"]
+        L = logits.shape[0]
+        outputs = {"pred_logits": logits[-1], "pred_boxes": boxes[-1],
+                   "aux_outputs": [{"pred_logits": logits[l], "pred_boxes": boxes[l]} for l in range(L - 1)]}
+        losses = criterion(outputs, targets, txt["token_mask"], positive_map)
+        losses["outputs"] = outputs
+        if V.ENABLED:                                             # groundingdino.py:621-640: under CONDITION_GATE the ff_gate parameters alone
+            gates = [v.reshape(-1)[0].to(dev).float() for k, v in self.state_dict().items() if ".qv_layer." in k and k.endswith(".ff_gate")]
+            if gates:
+                losses["loss_gate"] = float(V.get("GATE_REGULARIZATION_SCALE", 0.1)) * (1 - torch.stack(gates).abs()).sum() / len(gates)
+        return losses
+
     @torch.no_grad()
     def extract_query(self, samples=None, targets=None, query_images=None, visual_features=None, exclude_similar=False,
                       device=None, max_query_number=None):

@@ -462,9 +462,11 @@ def two_stage(P, cfg, mem16, text32, geo, txt):
     return ref_unsig.sigmoid(), topk, torch.gather(e32, 1, topk[..., None].expand(-1, -1, e32.shape[-1])), props.sigmoid()
 
 
-def decoder(P, cfg, mem16, text32, ref0, geo, txt, trace=None):
+def decoder(P, cfg, mem16, text32, ref0, geo, txt, trace=None, want_hs=False):
     """TransformerDecoder.forward (transformer.py:644-736) + DeformableTransformerDecoderLayer (:868-927), batch-first.
-    Returns (hs_last fp32 = norm(output of the last layer), refs: list of sigmoid boxes, refs[i] = input of layer i)."""
+    Returns (hs_last fp32 = norm(output of the last layer), refs: list of sigmoid boxes, refs[i] = input of layer i).
+    want_hs (the set criterion, `set_outputs`): a third result, norm(output) of EVERY layer (:730) -- the refinement below keeps using the
+    un-normed state (:722), only the aux heads see the normed one."""
     G = cfg.GROUNDINGDINO
     t = "transformer.decoder"
     D, M, nl = G.hidden_dim, G.nheads, G.dec_layers
@@ -477,7 +479,7 @@ def decoder(P, cfg, mem16, text32, ref0, geo, txt, trace=None):
     tvt_all = _vt(P, t + ".text_v_all", text16)                                               # [B, nl*D, T]
     tgt32 = P["tgt_embed32"][None].expand(B, -1, -1).contiguous()
     vr4 = torch.cat([geo["vr"], geo["vr"]], -1)[:, None]                                      # [B, 1, L, 4]
-    rp, refs, hs = ref0, [ref0], None
+    rp, refs, hs, hs_all = ref0, [ref0], None, []
     for i in range(nl):
         b = f"{t}.layers.{i}"
         ref_in = (rp[:, :, None] * vr4).contiguous()                                          # [B, nq, L, 4]
@@ -503,9 +505,20 @@ def decoder(P, cfg, mem16, text32, ref0, geo, txt, trace=None):
         if i < nl - 1:                                         # iterative box refinement (:716-727); the last update is unused
             rp = (_mlp(P, f"{t}.bbox_embed.{i}", t16, 3).float() + inverse_sigmoid(rp)).sigmoid()
             refs.append(rp)
+            if want_hs:
+                hs_all.append(_ln(P, t + ".norm", tgt32, want_y32=True))
         else:
             hs = _ln(P, t + ".norm", tgt32, want_y32=True)
-    return hs, refs
+    return (hs, refs, hs_all + [hs]) if want_hs else (hs, refs)
+
+
+def set_outputs(P, cfg, hs_all, refs, text32, txt):
+    """What the training forward hands its criterion (groundingdino.py:585-612): per decoder layer l the boxes bbox_embed[l](hs[l]) +
+    inverse_sigmoid(refs[l]) and the PRE-sigmoid token logits hs32[l] @ text32^T with -inf at masked tokens.
+    -> (logits [L, B, nq, T], boxes [L, B, nq, 4]) fp32, layer L - 1 the main output."""
+    boxes = torch.stack([(_mlp(P, f"bbox_embed.{l}", h16, 3).float() + inverse_sigmoid(refs[l])).sigmoid() for l, (h16, _) in enumerate(hs_all)])
+    logits = torch.stack([torch.matmul(h32, text32.transpose(1, 2)) for _, h32 in hs_all])
+    return logits.masked_fill(~txt["token_mask"][None, :, None, :], float("-inf")).contiguous(), boxes.contiguous()
 
 
 def heads(P, cfg, hs, ref_last, text32, txt):
@@ -541,14 +554,14 @@ def convert(prob, boxes, class_map, nan_labels, im_hw, box_threshold):
 
 
 def forward_device(P, cfg, SW, x, geo, txt, vision, idx, class_map, im_hw, max_kv=0, nan_labels=False, front=None, trace=None,
-                   src32=None):
+                   src32=None, want_set=False):
     """The device program: pixels [B,3,H,W] fp16 (channels_last) -> packed detections.  No host synchronisation inside.
     src32 [B, S, 256] fp32: the projected levels of a previous call with the same pixels (the evaluation loop sends every image
     once per chunk caption, engine/inference.py:605-625) -- Swin and the input projections are then skipped, `x` is ignored."""
     G = cfg.GROUNDINGDINO
     if src32 is not None:
         return _forward_from_src(P, cfg, src32, P["backbone.0.patch_embed.proj.weight"].dtype, geo, txt, vision, idx, class_map, im_hw,
-                                 max_kv, nan_labels, front, trace)
+                                 max_kv, nan_labels, front, trace, want_set)
     _mark("start")
     # the BERT layers below the first GCP block do not depend on the image: on a side stream under the Swin backbone
     # (B x 256 tokens per launch: they would otherwise run alone on a nearly empty chip)
@@ -564,10 +577,10 @@ def forward_device(P, cfg, SW, x, geo, txt, vision, idx, class_map, im_hw, max_k
     _mark("swin")
     src32 = input_projections(P, cfg, feats)
     _mark("input_proj")
-    return _forward_from_src(P, cfg, src32, x.dtype, geo, txt, vision, idx, class_map, im_hw, max_kv, nan_labels, front, trace)
+    return _forward_from_src(P, cfg, src32, x.dtype, geo, txt, vision, idx, class_map, im_hw, max_kv, nan_labels, front, trace, want_set)
 
 
-def _forward_from_src(P, cfg, src32, dt, geo, txt, vision, idx, class_map, im_hw, max_kv, nan_labels, front, trace):
+def _forward_from_src(P, cfg, src32, dt, geo, txt, vision, idx, class_map, im_hw, max_kv, nan_labels, front, trace, want_set=False):
     G = cfg.GROUNDINGDINO
     images = None
     if vision is not None:                                     # flatten_fpn_features (groundingdino.py:423-425)
@@ -585,6 +598,10 @@ def _forward_from_src(P, cfg, src32, dt, geo, txt, vision, idx, class_map, im_hw
     mem16, mem32, text32 = encoder(P, cfg, src32, text32, geo, txt, max_kv, None if trace is None else trace["enc"])
     ref0, topk, hs_enc, init_box = two_stage(P, cfg, mem16, text32, geo, txt)
     _mark("two_stage")
+    if want_set:                                               # the set criterion's operands instead of detections (forward_losses)
+        hs, refs, hs_all = decoder(P, cfg, mem16, text32, ref0, geo, txt, None if trace is None else trace["dec"], want_hs=True)
+        logits, boxes = set_outputs(P, cfg, hs_all, refs, text32, txt)
+        return {"set_logits": logits, "set_boxes": boxes, "srcs": src32}
     hs, refs = decoder(P, cfg, mem16, text32, ref0, geo, txt, None if trace is None else trace["dec"])
     _mark("decoder")
     prob, boxes = heads(P, cfg, hs, refs[-1], text32, txt)

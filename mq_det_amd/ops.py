@@ -89,6 +89,9 @@ _SIGNATURES = {
     "mq_atss_assign_fwd": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
     "mq_atss_box_loss_fwd": (_i, [_vp] * 11 + [_i] * 3 + [_vp]),
     "mq_token_focal_loss_fwd": (_i, [_vp] * 9 + [_i] * 6 + [_f, _f, _vp]),
+    "mq_set_cost_fwd": (_i, [_vp] * 6 + [_i] * 6 + [_f] * 4 + [_vp]),
+    "mq_hungarian_fwd": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    "mq_set_loss_fwd": (_i, [_vp] * 10 + [_i] * 6 + [_f, _f, _vp]),
 }
 # entry points with 16-bit operands also exist as <name>_bf16 (same signature; include/mqdet_hip.h MQ_BF16_TWIN)
 BF16_TWINS = ("mq_attn_fwd", "mq_attn_resident_fwd", "mq_attn_text_fwd", "mq_bert_attn_qkv_fwd", "mq_patch_embed_fwd", "mq_attn_chunked_fwd", "mq_window_attn_fwd", "mq_window_attn_qkv_fwd", "mq_gcp_sparse_attn_fwd", "mq_gcp_gate_residual_fwd", "mq_gcp_attn_fwd", "mq_vlfuse_i2t_fwd", "mq_vlfuse_t2i_fwd",
@@ -2064,3 +2067,73 @@ def token_focal_loss(tok, tk, tbias, matched, posmap, gt_off, text_mask, alpha, 
                                                       _ptr(partials), _ptr(loss), B, N, T, int(kv_max), posmap.shape[1], posmap.shape[0],
                                                       float(alpha), float(gamma), _stream()), "mq_token_focal_loss_fwd")
     return loss
+
+
+# ---- the set criterion of MQ-GroundingDINO, forward only (csrc/set_loss.hip; host side: mq_det_amd/set_loss.py)
+HUNGARIAN_MAX_QUERIES, SET_COST_MAX_TOKENS, SET_LOSS_ROWS = 1024, 512, 16
+
+
+def _set_args(logits, boxes, gt, posmap, gt_off):
+    _need_gpu(logits, boxes, gt, posmap, gt_off)
+    assert logits.dim() == 4 and boxes.shape == (*logits.shape[:3], 4) and logits.dtype == boxes.dtype == gt.dtype == posmap.dtype == torch.float32
+    L, B, nq, T = logits.shape
+    assert gt.dim() == 2 and gt.shape[1] == 4 and posmap.dim() == 2 and posmap.shape[0] == gt.shape[0] and gt_off.dtype == torch.int32
+    assert gt_off.numel() == B + 1
+    if posmap.shape[1] < T:
+        raise ValueError(f"set criterion: a positive map of {posmap.shape[1]} columns for logits of {T} text positions")
+    for t in (logits, boxes, gt, posmap, gt_off):
+        assert t.is_contiguous()
+    return L, B, nq, T, posmap.shape[1], gt.shape[0]
+
+
+def set_cost(logits, boxes, gt, posmap, gt_off, cost_class=1.0, cost_bbox=5.0, cost_giou=2.0, focal_alpha=0.25):
+    """The matching cost of HungarianMatcher (mq_set_cost_fwd): logits [L, B, nq, T] fp32 pre-sigmoid, boxes [L, B, nq, 4] cxcywh, gt [G, 4]
+    normalised cxcywh and posmap [G, Tpm] packed image after image, gt_off [B + 1] int32 -> cost [L, G, nq] fp32: the rows gt_off[b] ..
+    gt_off[b + 1] of layer l are the [G_b, nq] problem of (l, b)."""
+    lib = load_library()
+    L, B, nq, T, Tpm, G = _set_args(logits, boxes, gt, posmap, gt_off)
+    if T > SET_COST_MAX_TOKENS:
+        raise NotImplementedError(f"set criterion: {T} text positions, the cost kernel takes {SET_COST_MAX_TOKENS}")
+    cost = torch.empty(L, G, nq, dtype=torch.float32, device=logits.device)
+    with _timed("set_cost", logits.numel() * 4 + cost.numel() * 4):
+        _chk(lib.mq_set_cost_fwd(_ptr(logits), _ptr(boxes), _ptr(gt), _ptr(posmap), _ptr(gt_off), _ptr(cost), L, B, nq, T, Tpm, G,
+                                 float(cost_class), float(cost_bbox), float(cost_giou), float(focal_alpha), _stream()), "mq_set_cost_fwd")
+    return cost
+
+
+def hungarian(cost, gt_off, counts):
+    """Minimum-cost assignment of every (layer, image) block of `cost` [L, G, nq] fp32 (mq_hungarian_fwd); `counts` = the HOST list of gts per
+    image (what gt_off [B + 1] int32 holds on the device).  -> (match_q [L, G] int32: the query of each gt; q2g [L, B, nq] int32: the gt's index
+    inside its image or -1).  A problem with a non-finite entry: -1 for all its gts."""
+    lib = load_library()
+    _need_gpu(cost, gt_off)
+    assert cost.dim() == 3 and cost.dtype == torch.float32 and cost.is_contiguous() and gt_off.dtype == torch.int32 and gt_off.is_contiguous()
+    L, G, nq = cost.shape
+    B = len(counts)
+    assert gt_off.numel() == B + 1 and sum(counts) == G and all(c >= 0 for c in counts)
+    if nq > HUNGARIAN_MAX_QUERIES:
+        raise NotImplementedError(f"hungarian: {nq} queries, the solver takes {HUNGARIAN_MAX_QUERIES}")
+    if max(counts, default=0) > nq:
+        raise ValueError(f"hungarian: an image with {max(counts)} gt boxes for {nq} queries (every gt needs a query of its own)")
+    match_q = torch.empty(L, G, dtype=torch.int32, device=cost.device)
+    q2g = torch.empty(L, B, nq, dtype=torch.int32, device=cost.device)
+    with _timed("hungarian", cost.numel() * 4):
+        _chk(lib.mq_hungarian_fwd(_ptr(cost), _ptr(gt_off), _ptr(match_q), _ptr(q2g), L, B, nq, G, max(counts, default=0), _stream()),
+             "mq_hungarian_fwd")
+    return match_q, q2g
+
+
+def set_loss(logits, boxes, gt, posmap, gt_off, text_mask, q2g, match_q, alpha=0.25, gamma=2.0):
+    """loss_labels / loss_boxes of SetCriterion as raw sums (mq_set_loss_fwd): text_mask [B, T] int32, q2g [L, B, nq] and match_q [L, G] int32 as
+    `hungarian` returns them -> sums [L, 3] fp32 (token focal sum, S |src - tgt|, S (1 - GIoU) over the matched pairs)."""
+    lib = load_library()
+    L, B, nq, T, Tpm, G = _set_args(logits, boxes, gt, posmap, gt_off)
+    _need_gpu(text_mask, q2g, match_q)
+    assert text_mask.dtype == q2g.dtype == match_q.dtype == torch.int32 and text_mask.shape == (B, T) and q2g.shape == (L, B, nq)
+    assert match_q.shape == (L, G) and text_mask.is_contiguous() and q2g.is_contiguous() and match_q.is_contiguous()
+    partials = torch.empty(L * (-(-(B * nq) // SET_LOSS_ROWS)) * 3, dtype=torch.float32, device=logits.device)
+    sums = torch.empty(L, 3, dtype=torch.float32, device=logits.device)
+    with _timed("set_loss", logits.numel() * 4):
+        _chk(lib.mq_set_loss_fwd(_ptr(logits), _ptr(boxes), _ptr(gt), _ptr(posmap), _ptr(gt_off), _ptr(text_mask), _ptr(q2g), _ptr(match_q),
+                                 _ptr(partials), _ptr(sums), L, B, nq, T, Tpm, G, float(alpha), float(gamma), _stream()), "mq_set_loss_fwd")
+    return sums
